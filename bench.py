@@ -7,7 +7,13 @@ is resident in HBM before the timed region starts (BASELINE.json configs[1]).  O
 by torch.distributed.run for N > 1.  Pairs are independent, so ranks shard them with no data-path collective
 other than the gather of results ("weak" scaling: every rank owns --pairs pairs).
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task statement).
+A plain run measures the headline only: set-up, --warmup untimed steps, --steps timed steps, the result line.
+--full adds everything else the line used to carry: the CPU baselines (and the OpenCV probe), the `two_handles`
+record and, for the default configuration on one GPU, the `secondary` configurations (ORB 640x480, LoFTR 640x480
+split-bf16 and f32).  --dump-outputs DIR writes what the headline's last timed step computed (rank 0's match lists)
+as .npy files.
+
+Prints ONE JSON line on rank 0.
 """
 import argparse
 import json
@@ -327,9 +333,37 @@ def two_handle_leg(args, matcher, fm, W, H, P, ratio_or_thr, local_rank, dev, dA
                     "library); not the headline: `value` / `roofline` above are one handle, one stream"}
 
 
-def run_workload(args, matcher, W, H, P, ratio_or_thr, loftr_f32, rank, world, local_rank, dev, cdev, with_cpu):
+DUMP_BYTES_MAX = 48 << 20     # --dump-outputs: the match records beyond this are sampled by pair (seeded)
+
+
+def dump_outputs(d, packed, offs, cnt, P):
+    """What a caller of the timed path receives from one step (msf_pack_matches_device): the packed match records
+    (x1, y1, x2, y2) of every pair, the per-pair offsets into them and the per-pair counts (< 0: the pair overflowed
+    --cap).  Integers below 2^24, so float32 / float64 hold them exactly.  When the records exceed DUMP_BYTES_MAX as
+    float32, a fixed seeded sample of whole pairs is written instead, and `sample_pairs.npy` names them."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    offs_h = offs.cpu().numpy().astype(np.int64)
+    cnt_h = cnt.cpu().numpy()
+    recs = packed[:int(offs_h[P])].cpu().numpy()
+    pairs = np.arange(P)
+    if recs.nbytes > DUMP_BYTES_MAX:
+        keep = max(1, int(P * DUMP_BYTES_MAX // recs.nbytes))
+        pairs = np.sort(np.random.default_rng(20241016).choice(P, keep, replace=False))
+        recs = np.concatenate([recs[offs_h[i]:offs_h[i + 1]] for i in pairs])
+        offs_h = np.concatenate([[0], np.cumsum(offs_h[pairs + 1] - offs_h[pairs])])
+        cnt_h = cnt_h[pairs]
+        np.save(os.path.join(d, "sample_pairs.npy"), pairs.astype(np.float64))
+    np.save(os.path.join(d, "matches.npy"), recs.astype(np.float32).reshape(-1, 4))
+    np.save(os.path.join(d, "offsets.npy"), offs_h.astype(np.float64))
+    np.save(os.path.join(d, "counts.npy"), cnt_h.astype(np.float64))
+
+
+def run_workload(args, matcher, W, H, P, ratio_or_thr, loftr_f32, rank, world, local_rank, dev, cdev, with_cpu,
+                 full=False, dump_dir=None):
     """One metric configuration: P synthetic pairs per GPU resident in HBM, `warmup` untimed + `steps` timed steps on a
-    stream of its own.  Returns the result fields of one JSON line (rank 0) or None."""
+    stream of its own.  `full` adds the `two_handles` record; `dump_dir` receives the last timed step's outputs.
+    Returns the result fields of one JSON line (rank 0) or None."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -442,6 +476,9 @@ def run_workload(args, matcher, W, H, P, ratio_or_thr, loftr_f32, rank, world, l
         dt = float(tmax.item())
     res = None
     if rank == 0:
+        if dump_dir:
+            b = (args.steps - 1) % nbuf
+            dump_outputs(dump_dir, packed_b[b], offs_b[b], cnt, P)
         cnt_h = cnt.cpu().numpy()
         out_h = out.cpu().numpy()
         lists = [out_h[i, :max(cnt_h[i], 0)] for i in range(P)]
@@ -510,7 +547,7 @@ def run_workload(args, matcher, W, H, P, ratio_or_thr, loftr_f32, rank, world, l
                                   ", pipelined: step k's gather on its own stream beside step k+1's kernels")},
             "roofline": roofline,
         }
-        if world == 1 and not args.no_two_handles and not loftr_f32:
+        if full and world == 1 and not args.no_two_handles and not loftr_f32:
             try:
                 res["two_handles"] = two_handle_leg(args, matcher, fm, W, H, P, ratio_or_thr, local_rank, dev, dA, dB, out,
                                                     cnt, packed, offs, side)
@@ -626,8 +663,8 @@ def main():
     ap.add_argument("--ratio", type=float, default=0.6, help="Lowe ratio (the app uses 0.6, src/main.cpp:66)")
     ap.add_argument("--cap", type=int, default=1024, help="match-list capacity per pair")
     ap.add_argument("--matcher", default=None, choices=["orb", "loftr"],
-                    help="one workload only; default: the headline (ORB 1280x720) plus, on one GPU, the two other metric "
-                         "configurations (ORB 640x480, LoFTR 640x480) as `secondary`")
+                    help="one workload only; default: the headline (ORB 1280x720) plus, with --full on one GPU, the two "
+                         "other metric configurations (ORB 640x480, LoFTR 640x480) as `secondary`")
     ap.add_argument("--synth-mode", type=int, default=None,
                     help="synthetic texture: 0 blocky x8 (SURVEY 8d, ORB default), 1 smooth blobs (LoFTR default), 2 blocky x16")
     ap.add_argument("--cpu-threads", type=int, default=16)
@@ -640,10 +677,16 @@ def main():
     ap.add_argument("--threshold", type=float, default=0.15, help="LoFTR confidence threshold (dnnfeaturematcher.h:11)")
     ap.add_argument("--loftr-f32", action="store_true",
                     help="LoFTR: MSF_FLAG_LOFTR_F32 (every convolution on the f32 MFMA instead of split-bf16 products)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: CPU baselines + OpenCV probe, the `two_handles` record and (default "
+                         "configuration, one GPU) the `secondary` configurations; a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline's last timed step's outputs (rank 0's packed match lists, offsets, counts) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the `secondary` configurations")
     ap.add_argument("--no-two-handles", action="store_true",
-                    help="skip the extra `two_handles` record (steps alternating between two handles on two streams)")
+                    help="--full: skip the extra `two_handles` record (steps alternating between two handles on two streams)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (the measured configuration); gloo = rehearsal of the N > 1 code path "
                          "on a box with fewer GPUs than ranks (all ranks share cuda:0, results staged through host)")
@@ -653,6 +696,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
 
@@ -678,15 +723,16 @@ def main():
             dist.init_process_group("gloo")
     cdev = dev if args.backend == "nccl" else torch.device("cpu")   # where the collective's tensors live
 
-    with_cpu = not args.no_cpu_baseline and world == 1     # the CPU leg is timed on rank 0 of the 1-GPU run only
+    # the CPU leg is timed on rank 0 of the 1-GPU run only
+    with_cpu = args.full and not args.no_cpu_baseline and world == 1
     if args.matcher == "loftr":
         head = ("loftr", 640, 480, args.pairs or 256, args.threshold, args.loftr_f32)
     else:
         vga = (args.width, args.height) == (640, 480)
         head = ("orb", args.width, args.height, args.pairs or (4096 if vga else 1024), args.ratio, False)
     extra = []
-    if args.matcher is None and world == 1 and not args.no_secondary and (args.width, args.height) == (1280, 720) \
-            and args.pairs is None:
+    if args.full and args.matcher is None and world == 1 and not args.no_secondary \
+            and (args.width, args.height) == (1280, 720) and args.pairs is None:
         extra = [("orb", 640, 480, 4096, args.ratio, False), ("loftr", 640, 480, 256, args.threshold, False),
                  ("loftr", 640, 480, 256, args.threshold, True)]     # the exact-f32 LoFTR path, driver-timed too
     devices = [(local_rank, torch.cuda.get_device_name(local_rank))]
@@ -694,8 +740,10 @@ def main():
         gathered_dev = [None] * world
         dist.all_gather_object(gathered_dev, devices[0])
         devices = gathered_dev
-    r = run_workload(args, *head, rank, world, local_rank, dev, cdev, with_cpu)
-    secondary = [run_workload(args, *w, rank, world, local_rank, dev, cdev, with_cpu and not w[5]) for w in extra]
+    r = run_workload(args, *head, rank, world, local_rank, dev, cdev, with_cpu, full=args.full,
+                     dump_dir=args.dump_outputs)
+    secondary = [run_workload(args, *w, rank, world, local_rank, dev, cdev, with_cpu and not w[5], full=args.full)
+                 for w in extra]
     if rank == 0:
         r["config"].update({"ranks": world, "rccl_ranks": world if (world > 1 and args.backend == "nccl") else 0,
                             "collective_backend": (args.backend if world > 1 else None),
