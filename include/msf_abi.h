@@ -90,10 +90,15 @@ typedef struct msf_config {
                                 2 P rows of about 3.5 MB at 1280x720 -- and key points + descriptors (128 KB) per feature
                                 slot, of which there are 4 P + 64 (2 P caller-visible, 2 P scratch of the stateless calls,
                                 64 of the frame cache): 7.8 GB at P = 1024 (measured, tests/test_orb_gpu.py; round 4: 10.4,
-                                round 3: 20).  A level's candidate list holds w h / 64 entries (what the output-sensitive
-                                FAST pass lists); a level that needs more -- a dense second pass over a frame of noise --
-                                takes a full-size list from a pool shared by the call, and a call that exhausts the pool
-                                returns MSF_ERR_CAPACITY for the frames concerned (n_out = -1), never a short list.
+                                round 3: 20).  A level's candidate list holds w h / 64 entries, at least 8192 (what the
+                                output-sensitive FAST pass lists; a dense second pass lists only the level's retainBest(2N)
+                                survivors into it), so no frame depends on the others of its call.  ORB capacities: a
+                                frame comes back with n_out = -1 (MSF_ERR_CAPACITY), never a short list, exactly when it
+                                has more than 2048 final key points, or a level keeps more than min(8192, w h / 8) key
+                                points after retainBest(2N) on the FAST score (ties included), or -- a call of fewer than
+                                eight frames or MSF_FLAG_FAST_DENSE only -- a level has more than w h / 8 strict FAST
+                                maxima (w h / 8: at least 4096).  The same in every call form, at any batch size or
+                                position.
                                 LoFTR: about 20 MB of activations per pair of a backbone chunk (<= 256) */
   uint32_t flags;
   const char* weights_path;  /* LoFTR: the model file, as DNNFeatureMatcher's model_file_path (dnnfeaturematcher.cpp:11-21):

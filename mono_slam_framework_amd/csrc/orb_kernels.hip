@@ -292,12 +292,12 @@ struct FastSmem {
   uint32_t nbd, lcount, gbase;   // nbd: brighter count (low 16) | darker count (high 16)
 };
 
-// ---- where the candidate list of (frame, level) lives (r05): cmap[slot * 8 + level] = (first entry, capacity) in the
-// candidate arrays -- the level's primary list inside the frame's work row, or a block of the pool (orb_pipeline.h)
-__global__ __launch_bounds__(256) void k_cand_reset(OrbGeometry g, OrbPrimLists prim, uint2* cmap_rows, uint32_t* pool_cnt,
-                                                    int n_frames, int dense) {
+// ---- where the candidate list of (frame, level) lives: cmap[slot * 8 + level] = (first entry, capacity) in the
+// candidate arrays -- the level's primary list inside the frame's work row, or (a dense call) the level's full-capacity
+// list inside the frame's region of the pool (orb_pipeline.h)
+__global__ __launch_bounds__(256) void k_cand_reset(OrbGeometry g, OrbPrimLists prim, uint2* cmap_rows, int n_frames,
+                                                    int dense) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i == 0) *pool_cnt = 0u;
   if (i >= n_frames * kOrbLevels) return;
   const int row = i / kOrbLevels, l = i - row * kOrbLevels;
   if (l >= g.nlevels) { cmap_rows[i] = make_uint2(0u, 0u); return; }
@@ -306,23 +306,18 @@ __global__ __launch_bounds__(256) void k_cand_reset(OrbGeometry g, OrbPrimLists 
   cmap_rows[i] = dense ? make_uint2((uint32_t)(g.pool_base + (long long)row * g.cand_total + L.cand_off), (uint32_t)L.cand_cap)
                        : make_uint2((uint32_t)((long long)row * g.prim_total + prim.off[l]), (uint32_t)prim.cap[l]);
 }
-// one lane: (slot, level) moves to a pool region of its full capacity (before its dense pass); false: the pool is exhausted
-__device__ __forceinline__ bool cand_take_block(const OrbGeometry& g, uint2* cmap, uint32_t* pool_cnt, int idx, int l) {
-  const uint32_t cap = (uint32_t)g.lv[l].cand_cap;              // (a multiple of 16: regions stay 16-byte aligned)
-  const uint32_t at = atomicAdd(pool_cnt, cap);
-  if (at > g.pool_entries || cap > g.pool_entries - at) return false;
-  cmap[idx] = make_uint2((uint32_t)(g.pool_base + (long long)at), cap);
-  return true;
-}
-
 // One tile of level l of frame fi with score threshold tau (even, >= kFastT): emits exactly the strict 3x3 maxima whose
 // score is >= tau.  With tau = kFastT that is FAST_t<16> + NMS; with a larger tau it is the subset retainBest(2N) can
 // still keep: a pixel whose score is below tau gets 0 in the score tile, which is what a maximum with score >= tau
 // needs to know about it (it loses), and every pixel with score >= tau passes the prefilter at tau and is scored exactly.
 // All threads of the workgroup must call this together; the LDS block may be reused after the call returns.
+// The dense pass of a streaming call (k_fast_redo) runs it twice per tile at tau = kFastT: with `hist` it appends
+// nothing and counts the scores of the maxima into the (frame, level)'s 256-bin histogram instead; with emit_min > 0 it
+// appends only the maxima scoring >= emit_min (NMS still sees every corner at tau: the set is the threshold-tau one, cut).
 __device__ __forceinline__ void fast_tile(const OrbGeometry& g, const FrameSrc& src, const uint8_t* pyr, int fi, int l,
                                           int t, int tau, uint32_t* cand_cnt, uint32_t* cand_key, uint8_t* cand_sc,
-                                          const uint2* cmap, FastSmem& S_) {
+                                          const uint2* cmap, FastSmem& S_, uint32_t* hist = nullptr,
+                                          uint32_t emit_min = 0u) {
   uint8_t* px = S_.px;
   uint8_t* sc = S_.sc;
   uint16_t* list1 = S_.list1;
@@ -457,6 +452,13 @@ __device__ __forceinline__ void fast_tile(const OrbGeometry& g, const FrameSrc& 
         } else {
           keep &= 0x80808080u;
         }
+        if (emit_min > 0u) {   // uniform (a kernel argument)
+          uint32_t ge = 0u;
+#pragma unroll
+          for (int b = 0; b < 4; b++)
+            if (((C >> (8 * b)) & 0xFFu) >= emit_min) ge |= 0x80u << (8 * b);
+          keep &= ge;
+        }
       }
       const uint32_t mine = __popc(keep);
       uint32_t k = reserve_packed(mine, &S_.lcount, lane);
@@ -468,7 +470,10 @@ __device__ __forceinline__ void fast_tile(const OrbGeometry& g, const FrameSrc& 
     }
     __syncthreads();
     const uint32_t n = S_.lcount;
-    if (n != 0) {   // uniform
+    if (hist) {     // uniform: count, do not list
+      uint32_t* const hl = hist + (size_t)(slot * kOrbLevels + l) * 256u;
+      for (uint32_t i = tid; i < n; i += kFastThreads) atomicAdd(&hl[llist[i].y], 1u);
+    } else if (n != 0) {   // uniform
       if (tid == 0) S_.gbase = atomicAdd(&cand_cnt[slot * kOrbLevels + l], n);
       __syncthreads();
       const uint32_t base = S_.gbase;
@@ -1457,7 +1462,7 @@ __global__ __launch_bounds__(64) void k_walk(OrbGeometry g, FrameSrc src, uint8_
 // After the walker: tau[idx] is the largest threshold any strip of the (frame, level) ran at, and every strict maximum
 // with a score at or above it is in the candidate list (strips that ran lower also left smaller ones).  If fewer than 2N
 // reach it, retainBest(2N) would cut below what was searched completely: the level is queued for the dense pass (its
-// candidate list restarts from empty).  One wave per (frame, level).
+// candidate list restarts from empty).  So is a level whose list overflowed its primary list.  One wave per (frame, level).
 __global__ __launch_bounds__(64) void k_fast_check(OrbGeometry g, int slot0, int n_frames, uint32_t* tau, uint32_t* tau_first,
                                                    uint32_t* cand_cnt, const uint8_t* cand_sc, const uint2* cmap,
                                                    uint32_t* redo_cnt, uint32_t* redo_list, const uint32_t* qstat) {
@@ -1468,8 +1473,8 @@ __global__ __launch_bounds__(64) void k_fast_check(OrbGeometry g, int slot0, int
   const uint32_t T = max(tau[idx], qstat[(size_t)idx * kQStat + kQTau]);   // the largest threshold any strip ran at
   const OrbLevelInfo L = g.lv[l];
   const uint2 cm = cmap[idx];
-  // a primary list that overflowed is incomplete: the level takes the dense pass (with a full-capacity block) like one
-  // that holds too few strong corners
+  // a primary list that overflowed is incomplete: the level takes the dense pass like one that holds too few strong
+  // corners (the dense pass lists only the level's stage-1 candidates: they fit whenever stage 1 fits kS1Cap)
   const bool over = cand_cnt[idx] > cm.y;
   const uint32_t n = min(cand_cnt[idx], cm.y);
   const uint8_t* scs = cand_sc + cm.x;
@@ -1496,12 +1501,18 @@ __global__ __launch_bounds__(64) void k_fast_check(OrbGeometry g, int slot0, int
 }
 
 // Dense second pass over the queued (frame, level)s: fixed grid, unit u = (queue entry, tile index); tile indices past
-// the level's tile count are skipped (levels differ in size; the queue is short or empty in practice).
+// the level's tile count are skipped (levels differ in size; the queue is short or empty in practice).  Two launches:
+// the first (hist != null) counts the scores of the level's maxima at fastThreshold into its 256-bin histogram and lists
+// nothing; k_redo_thr picks the score to list from: every maximum if they all fit the level's primary list, else the
+// level's retainBest(2N) cut; the second (emit_thr != null) lists the maxima scoring at or above it into the primary
+// list.  A cut list is exactly the level's stage 1, so the list holds it whenever stage 1 fits kS1Cap (primary lists
+// hold at least kS1Cap entries, or the level's full list): no level needs more room than its own, whatever the other
+// frames of the call are.
 __global__ __launch_bounds__(kFastThreads) void k_fast_redo(OrbGeometry g, FrameSrc src, const uint8_t* pyr,
                                                             const uint32_t* __restrict__ redo_cnt,
                                                             const uint32_t* __restrict__ redo_list, int max_tiles,
                                                             uint32_t* cand_cnt, uint32_t* cand_key, uint8_t* cand_sc,
-                                                            const uint2* cmap) {
+                                                            const uint2* cmap, uint32_t* hist, const uint32_t* emit_thr) {
   __shared__ FastSmem sm;
   const uint32_t n = *redo_cnt;
   const unsigned long long units = (unsigned long long)n * (unsigned)max_tiles;
@@ -1514,28 +1525,52 @@ __global__ __launch_bounds__(kFastThreads) void k_fast_redo(OrbGeometry g, Frame
     const int t = (int)(u % (unsigned)max_tiles);
     const int fi = (int)(item / kOrbLevels), l = (int)(item % kOrbLevels);
     if (t >= g.lv[l].tiles_x * g.lv[l].tiles_y) continue;   // uniform
-    fast_tile(g, src, pyr, fi, l, t, kFastT, cand_cnt, cand_key, cand_sc, cmap, sm);
+    uint32_t emit_min = 0u;
+    if (emit_thr) {
+      emit_min = emit_thr[(src.slot0 + fi) * kOrbLevels + l];
+      if (emit_min > 255u) continue;                         // uniform: retainBest(0) keeps nothing
+    }
+    fast_tile(g, src, pyr, fi, l, t, kFastT, cand_cnt, cand_key, cand_sc, cmap, sm, hist, emit_min);
     __syncthreads();
   }
 }
 
-// After the dense second pass: a redone level whose candidates did not fit its primary list (a frame of noise: tens of
-// thousands of maxima; a smooth frame's dense list is short) moves to a pool region of full capacity and is queued once
-// more.  One thread per entry of the first queue.  Pool exhausted: the frame is flagged (MSF_ERR_CAPACITY), never a short list.
-__global__ __launch_bounds__(256) void k_redo_overflow(OrbGeometry g, int slot0, uint32_t* cand_cnt, uint2* cmap,
-                                                       uint32_t* pool_cnt, uint32_t* status, const uint32_t* redo_cnt,
-                                                       const uint32_t* redo_list, uint32_t* redo2_cnt, uint32_t* redo2_list) {
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= *redo_cnt) return;
-  const uint32_t item = redo_list[i];
-  const int fi = (int)(item / kOrbLevels), l = (int)(item % kOrbLevels);
-  const int idx = (slot0 + fi) * kOrbLevels + l;
-  if (cand_cnt[idx] <= cmap[idx].y) return;
-  if ((uint32_t)g.lv[l].cand_cap > cmap[idx].y && cand_take_block(g, cmap, pool_cnt, idx, l)) {
-    cand_cnt[idx] = 0;
-    redo2_list[atomicAdd(redo2_cnt, 1u)] = item;
-  } else {
-    atomicOr(&status[slot0 + fi], kStatusOverflow);
+// Between the two dense launches: per queued (frame, level) the score the second launch lists from.  0 (every maximum)
+// when all the level's maxima fit its primary list -- the list is then the complete one, as a dense call makes it;
+// otherwise the cut of KeyPointsFilter::retainBest(2N) from the score histogram -- the largest score b with (maxima
+// scoring >= b) >= 2N (ties kept); 256 (list none) when 2N = 0 -- as k_thr_harris computes it from a list, which then
+// finds the same cut again.  Leaves the histogram zeroed for the next call (it is zeroed once at init; only the first
+// dense launch adds to it).  One wave per queue entry, a fixed grid walking the queue.
+__global__ __launch_bounds__(64) void k_redo_thr(OrbGeometry g, int slot0, const uint32_t* __restrict__ redo_cnt,
+                                                 const uint32_t* __restrict__ redo_list, const uint2* cmap, uint32_t* hist,
+                                                 uint32_t* emit_thr) {
+  const uint32_t n = *redo_cnt;
+  const int lane = threadIdx.x;
+  for (uint32_t q = blockIdx.x; q < n; q += gridDim.x) {
+    const uint32_t item = redo_list[q];
+    const int fi = (int)(item / kOrbLevels), l = (int)(item % kOrbLevels);
+    const int idx = (slot0 + fi) * kOrbLevels + l;
+    uint4* const hl = reinterpret_cast<uint4*>(hist + (size_t)idx * 256u);
+    const uint4 hv = hl[lane];                               // lane i owns bins 4i .. 4i+3
+    hl[lane] = make_uint4(0u, 0u, 0u, 0u);
+    const uint32_t keep = 2u * (uint32_t)g.lv[l].quota;
+    uint32_t above = hv.x + hv.y + hv.z + hv.w;              // -> maxima in the bins of lanes > lane
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t up = __shfl_down(above, o);
+      if (lane + o < 64) above += up;
+    }
+    const uint32_t total = __shfl(above, 0);
+    above -= hv.x + hv.y + hv.z + hv.w;
+    const uint32_t c3 = above + hv.w, c2 = c3 + hv.z, c1 = c2 + hv.y, c0 = c1 + hv.x;   // maxima scoring >= 4i+3 .. 4i
+    const int mine = c3 >= keep ? 4 * lane + 3 : c2 >= keep ? 4 * lane + 2 : c1 >= keep ? 4 * lane + 1 : c0 >= keep ? 4 * lane : -1;
+    const unsigned long long ok = __ballot(mine >= 0);
+    uint32_t thr = 0;                                        // at most 2N maxima, or all fit: list them all
+    if (total > keep && total > cmap[idx].y) {
+      thr = 256;                                             // keep == 0: list none
+      if (keep > 0 && ok) thr = (uint32_t)__shfl(mine, 63 - __builtin_clzll(ok));
+    }
+    if (lane == 0) emit_thr[idx] = thr;
   }
 }
 
@@ -2297,9 +2332,9 @@ void OrbPipeline::destroy() {
   hipFree(d_tau_); hipFree(d_redo_); hipFree(d_qstat_); hipFree(d_walk_abort_);
   if (h_walk_abort_) hipHostFree(h_walk_abort_);
   d_tau_ = nullptr; d_redo_ = nullptr; d_qstat_ = nullptr; d_walk_abort_ = nullptr; h_walk_abort_ = nullptr;
-  hipFree(d_pyr_); hipFree(d_tab_); hipFree(d_cand_cnt_); hipFree(d_cand_); hipFree(d_cand_sc_); hipFree(d_cmap_); hipFree(d_pool_cnt_); hipFree(d_qres_); hipFree(d_done_); hipFree(d_s1_cnt_); hipFree(d_s1_);
+  hipFree(d_pyr_); hipFree(d_tab_); hipFree(d_cand_cnt_); hipFree(d_cand_); hipFree(d_cand_sc_); hipFree(d_cmap_); hipFree(d_redo_hist_); hipFree(d_redo_thr_); hipFree(d_qres_); hipFree(d_done_); hipFree(d_s1_cnt_); hipFree(d_s1_);
   hipFree(d_kp_); hipFree(d_desc_); hipFree(d_kp_cnt_); hipFree(d_status_);
-  d_pyr_ = nullptr; d_tab_ = nullptr; d_cand_cnt_ = nullptr; d_cand_ = nullptr; d_cand_sc_ = nullptr; d_cmap_ = nullptr; d_pool_cnt_ = nullptr; d_qres_ = nullptr; d_done_ = nullptr; d_s1_cnt_ = nullptr;
+  d_pyr_ = nullptr; d_tab_ = nullptr; d_cand_cnt_ = nullptr; d_cand_ = nullptr; d_cand_sc_ = nullptr; d_cmap_ = nullptr; d_redo_hist_ = nullptr; d_redo_thr_ = nullptr; d_qres_ = nullptr; d_done_ = nullptr; d_s1_cnt_ = nullptr;
   d_s1_ = nullptr; d_kp_ = nullptr; d_desc_ = nullptr; d_kp_cnt_ = nullptr; d_status_ = nullptr;
   if (ev_ok_) {
     for (auto& set : evr_)
@@ -2417,9 +2452,10 @@ std::string OrbPipeline::init(int width, int height, int max_slots, bool blur_ha
     cand += cap;
     // the output-sensitive pass lists the maxima at or above the level's threshold -- about a thousand at 1280 x 720
     // against ~20 000 maxima in all --: the primary list is an eighth of the full one (a list that overflows all the same
-    // sends its level to the dense pass, k_fast_check)
+    // sends its level to the dense pass, k_fast_check), and at least kS1Cap: the dense pass lists the level's stage 1
+    // into it, so every stage 1 that fits kS1Cap fits its primary list
     int pcap = (int)((long long)L.w * L.h / 64);
-    if (pcap < 4096) pcap = 4096;
+    if (pcap < kS1Cap) pcap = kS1Cap;
     pcap = (pcap + 15) & ~15;
     // small levels keep their full capacity (little memory, and small levels are the ones that take the dense pass:
     // their thresholds rest on few corners): only lists above 16 K entries are cut
@@ -2549,24 +2585,18 @@ std::string OrbPipeline::init(int width, int height, int max_slots, bool blur_ha
   MSF_HIP_TRY(hipMalloc(&d_cand_cnt_, Wk * kOrbLevels * sizeof(uint32_t)));
   MSF_HIP_TRY(hipMalloc(&d_tau_, 2 * Wk * kOrbLevels * sizeof(uint32_t)));
   MSF_HIP_TRY(hipMemset(d_tau_, 0, 2 * Wk * kOrbLevels * sizeof(uint32_t)));
-  MSF_HIP_TRY(hipMalloc(&d_redo_, 2 * (1 + Wk * kOrbLevels) * sizeof(uint32_t)));   // two queues: dense pass, dense pass again from the pool
+  MSF_HIP_TRY(hipMalloc(&d_redo_, (1 + Wk * kOrbLevels) * sizeof(uint32_t)));   // the dense-pass queue
+  MSF_HIP_TRY(hipMalloc(&d_redo_hist_, Wk * kOrbLevels * 256 * sizeof(uint32_t)));
+  MSF_HIP_TRY(hipMemset(d_redo_hist_, 0, Wk * kOrbLevels * 256 * sizeof(uint32_t)));   // k_redo_thr leaves it zeroed
+  MSF_HIP_TRY(hipMalloc(&d_redo_thr_, Wk * kOrbLevels * sizeof(uint32_t)));
   MSF_HIP_TRY(hipMalloc(&d_qstat_, Wk * kOrbLevels * kQStat * sizeof(uint32_t)));
   MSF_HIP_TRY(hipMemset(d_qstat_, 0, Wk * kOrbLevels * kQStat * sizeof(uint32_t)));
   {
-    // candidate arrays: a primary region per work row + the pool.  The pool serves (a) the (frame, level)s that take the
-    // dense second pass -- 0 to 8 of 2 048 in the measured batches; sized for an eighth of all of them at full capacity,
-    // at least 64 level-0 lists -- and (b) dense CALLS, whose frames lay their full-capacity regions over it: every row
-    // with MSF_FLAG_FAST_DENSE, at most stream_min_frames - 1 frames otherwise.
+    // candidate arrays: a primary region per work row + the pool.  The pool only serves dense CALLS, whose frames lay
+    // their full-capacity regions over it: every row with MSF_FLAG_FAST_DENSE, at most stream_min_frames - 1 frames
+    // otherwise.  (The dense second pass of a streaming call lists into the level's primary list: k_fast_redo.)
     const long long dense_rows = force_tau_ == kFastT ? (long long)Wk : std::min<long long>((long long)Wk, std::max(stream_min_frames_ - 1, 0));
-    long long redo_entries = std::max<long long>((long long)Wk * g.cand_total / 8, 64ll * g.lv[0].cand_cap);
-    redo_entries = std::min<long long>(redo_entries, (long long)Wk * g.cand_total);
-    // (MSF_ORB_POOL_ENTRIES, tests: a pool too small for what a batch needs must end in MSF_ERR_CAPACITY, never in a
-    // short list; batches that force most levels through the dense pass ask for more)
-    if (const char* e = getenv("MSF_ORB_POOL_ENTRIES")) {
-      const long long v = atoll(e);
-      if (v >= 0) redo_entries = std::min<long long>(v, (long long)Wk * g.cand_total);
-    }
-    const long long pool_entries_ = std::max(std::max<long long>(redo_entries, 16), dense_rows * g.cand_total);
+    const long long pool_entries_ = std::max<long long>(dense_rows * g.cand_total, 16);
     g.pool_base = (long long)Wk * g.prim_total;
     const long long total = g.pool_base + pool_entries_;
     if (total >= (1ll << 32)) return "ORB candidate arrays exceed 2^32 entries: reduce max_batch_pairs";
@@ -2575,8 +2605,6 @@ std::string OrbPipeline::init(int width, int height, int max_slots, bool blur_ha
     MSF_HIP_TRY(hipMalloc(&d_cand_sc_, (size_t)total));
     MSF_HIP_TRY(hipMalloc(&d_cmap_, Wk * kOrbLevels * sizeof(uint2)));
     MSF_HIP_TRY(hipMemset(d_cmap_, 0, Wk * kOrbLevels * sizeof(uint2)));
-    MSF_HIP_TRY(hipMalloc(&d_pool_cnt_, 16));
-    MSF_HIP_TRY(hipMemset(d_pool_cnt_, 0, 16));
   }
   MSF_HIP_TRY(hipMalloc(&d_walk_abort_, 16));
   MSF_HIP_TRY(hipMemset(d_walk_abort_, 0, 16));
@@ -2663,10 +2691,11 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
   uint32_t* const d_qstat_ = this->d_qstat_ - back * kOrbLevels * kQStat;
   uint32_t* const d_s1_cnt_ = this->d_s1_cnt_ - back * kOrbLevels;
   uint4* const d_s1_ = this->d_s1_ - back * g.s1_total;
+  uint32_t* const d_redo_hist_ = this->d_redo_hist_ - back * kOrbLevels * 256;
+  uint32_t* const d_redo_thr_ = this->d_redo_thr_ - back * kOrbLevels;
   if ((e = hipMemsetAsync(this->d_cand_cnt_, 0, (size_t)n * kOrbLevels * 4, st))) return e;
   if ((e = hipMemsetAsync(d_status_ + src.slot0, 0, (size_t)n * 4, st))) return e;
   if ((e = hipMemsetAsync(d_redo_, 0, 4, st))) return e;
-  if ((e = hipMemsetAsync(d_redo_ + 1 + (size_t)work_frames_ * kOrbLevels, 0, 4, st))) return e;
   if (evs) hipEventRecord(evs[0], st);
   uint32_t* tau = d_tau_ - back * kOrbLevels;
   uint32_t* tau_first = d_tau_ + (ptrdiff_t)work_frames_ * kOrbLevels - back * kOrbLevels;
@@ -2678,7 +2707,7 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
   // where each (frame, level)'s candidate list lives in this call (k_cand_reset): its primary list, or -- a dense call --
   // the frame's full-capacity region in the pool
   if (dense && (long long)n * g.cand_total > (long long)g.pool_entries) return hipErrorInvalidValue;   // (cannot happen: see init)
-  hipLaunchKernelGGL(k_cand_reset, dim3((n * kOrbLevels + 255) / 256), dim3(256), 0, st, g, prim_, this->d_cmap_, d_pool_cnt_, n, dense ? 1 : 0);
+  hipLaunchKernelGGL(k_cand_reset, dim3((n * kOrbLevels + 255) / 256), dim3(256), 0, st, g, prim_, this->d_cmap_, n, dense ? 1 : 0);
   const int dyn = (fast_two_part_ && force_tau == 0) ? 1 : 0;
   bool fused = fused_ && !dense && g.total_tiles > 0;
   for (int l = 1; l < g.nlevels; l++) fused = fused && g.lv[l].wk_fused != 0;
@@ -2710,6 +2739,7 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
                        tau2_margin_pct_, dyn, force_tau, predict_pct, chain, resize_mask, test_stall_frame_);
   };
   last_fused_ = fused;
+  last_dense_ = dense;
   if (!dense && g.total_tiles > 0) {
     // the walker's per-(frame, level) state starts from zero: histograms, counters, "threshold published" words
     if ((e = hipMemsetAsync(this->d_qstat_, 0, (size_t)n * kOrbLevels * kQStat * 4, st))) return e;
@@ -2753,15 +2783,15 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
     long long units = (long long)n * kOrbLevels * g.max_level_tiles;
     unsigned grid = (unsigned)(units < 2048 ? units : 2048);
     grid = (grid + 7u) & ~7u;
+    // the dense pass of the queued levels: score histogram, then the level's maxima into its own primary list -- all of
+    // them if they fit, else those at or above the retainBest(2N) cut (all three launches find an empty queue in nearly
+    // every call)
     hipLaunchKernelGGL(k_fast_redo, dim3(grid), dim3(kFastThreads), 0, st, g, src, d_pyr_, d_redo_, d_redo_ + 1,
-                       g.max_level_tiles, d_cand_cnt_, d_cand_, d_cand_sc_, d_cmap_);
-    // a redone level that overflowed its primary list: once more, into a full-capacity region of the pool (both launches
-    // find an empty queue in nearly every call)
-    uint32_t* const redo2 = d_redo_ + 1 + (size_t)work_frames_ * kOrbLevels;
-    hipLaunchKernelGGL(k_redo_overflow, dim3((n * kOrbLevels + 255) / 256), dim3(256), 0, st, g, src.slot0, d_cand_cnt_, d_cmap_,
-                       d_pool_cnt_, d_status_, d_redo_, d_redo_ + 1, redo2, redo2 + 1);
-    hipLaunchKernelGGL(k_fast_redo, dim3(grid), dim3(kFastThreads), 0, st, g, src, d_pyr_, redo2, redo2 + 1,
-                       g.max_level_tiles, d_cand_cnt_, d_cand_, d_cand_sc_, d_cmap_);
+                       g.max_level_tiles, d_cand_cnt_, d_cand_, d_cand_sc_, d_cmap_, d_redo_hist_, (const uint32_t*)nullptr);
+    hipLaunchKernelGGL(k_redo_thr, dim3((unsigned)std::min<long long>((long long)n * kOrbLevels, 1024)), dim3(64), 0, st, g,
+                       src.slot0, d_redo_, d_redo_ + 1, d_cmap_, d_redo_hist_, d_redo_thr_);
+    hipLaunchKernelGGL(k_fast_redo, dim3(grid), dim3(kFastThreads), 0, st, g, src, d_pyr_, d_redo_, d_redo_ + 1,
+                       g.max_level_tiles, d_cand_cnt_, d_cand_, d_cand_sc_, d_cmap_, (uint32_t*)nullptr, d_redo_thr_);
   }
   if (evs) hipEventRecord(evs[2], st);
   hipLaunchKernelGGL(k_thr_harris, dim3(g.nlevels, n), dim3(dense ? 256 : 64), 0, st, g, src, d_pyr_,
@@ -2923,6 +2953,50 @@ int OrbPipeline::debug_get(int what, int slot, int level, void* host_out, size_t
       // the sampled quarter of a two-part streaming pass also lists corners below the level's final threshold
       uint32_t tfin = 0;
       hipMemcpy(&tfin, d_tau_ + (size_t)row * kOrbLevels + level, 4, hipMemcpyDeviceToHost);
+      // the dense pass of a streaming call (tau 20) lists a level whose maxima did not fit its primary list only from the
+      // retainBest(2N) cut on (k_redo_thr); this view makes the complete list again, into a full-capacity list of its
+      // own -- for levels >= 1, whose pixels are in the pyramid (level 0 is the caller's frame: its view stays the cut list)
+      uint32_t cut = 0;
+      if (!last_dense_ && tfin == (uint32_t)kFastT && level >= 1)
+        hipMemcpy(&cut, d_redo_thr_ + (size_t)row * kOrbLevels + level, 4, hipMemcpyDeviceToHost);
+      if (cut > 0u) {
+        const OrbLevelInfo& L = g.lv[level];
+        const size_t cap_l = (size_t)L.cand_cap;
+        uint32_t* d_tmp = nullptr;   // [2] queue (count, item) | [8] counts | [8] uint2 map | keys [cap_l] | scores [cap_l]
+        const size_t words = 2 + kOrbLevels + 2 * kOrbLevels + cap_l + (cap_l + 3) / 4;
+        if (hipMalloc(&d_tmp, words * 4) != hipSuccess) return fail("hipMalloc failed in debug_get");
+        if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize failed in debug_get");
+        uint32_t head[2 + kOrbLevels + 2 * kOrbLevels] = {};
+        head[0] = 1u;
+        head[1] = (uint32_t)(row * kOrbLevels + level);
+        head[2 + kOrbLevels + 2 * level] = (uint32_t)(2 + 3 * kOrbLevels);        // the list starts right behind the map
+        head[2 + kOrbLevels + 2 * level + 1] = (uint32_t)cap_l;
+        hipMemcpy(d_tmp, head, sizeof(head), hipMemcpyHostToDevice);
+        // the kernels index per-(frame, level) arrays by slot = slot0 + frame: bases moved back by `slot` entries
+        const ptrdiff_t back = (ptrdiff_t)slot * kOrbLevels;
+        uint32_t* const cnt = d_tmp + 2 - back;
+        const uint2* const map = reinterpret_cast<const uint2*>(d_tmp + 2 + kOrbLevels) - back;
+        uint32_t* const keys = d_tmp;                                             // map entries are absolute offsets
+        uint8_t* const scs = reinterpret_cast<uint8_t*>(d_tmp + 2 + 3 * kOrbLevels + cap_l) - (2 + 3 * kOrbLevels);
+        const uint8_t* const pyr = d_pyr_ - (ptrdiff_t)last_src_.slot0 * g.pyr_bytes;
+        const int tiles = L.tiles_x * L.tiles_y;
+        if (tiles > 0)
+          hipLaunchKernelGGL(k_fast_redo, dim3((unsigned)((std::min(tiles, 2048) + 7) & ~7)), dim3(kFastThreads), 0, 0, g,
+                             last_src_, pyr, d_tmp, d_tmp + 1, tiles, cnt, keys, scs, map, (uint32_t*)nullptr,
+                             (const uint32_t*)nullptr);
+        hipError_t e2 = hipDeviceSynchronize();
+        n = 0;
+        if (e2 == hipSuccess) e2 = hipMemcpy(&n, d_tmp + 2 + level, 4, hipMemcpyDeviceToHost);
+        if (n > (uint32_t)cap_l) n = (uint32_t)cap_l;
+        tk.assign(n, 0u);
+        ts.assign(n, 0u);
+        if (e2 == hipSuccess && n) {
+          e2 = hipMemcpy(tk.data(), d_tmp + 2 + 3 * kOrbLevels, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+          if (e2 == hipSuccess) e2 = hipMemcpy(ts.data(), d_tmp + 2 + 3 * kOrbLevels + cap_l, n, hipMemcpyDeviceToHost);
+        }
+        hipFree(d_tmp);
+        if (e2 != hipSuccess) return fail("dense FAST pass failed in debug_get");
+      }
       std::vector<int32_t> o;
       o.reserve(n * 3);
       for (uint32_t i = 0; i < n; i++)

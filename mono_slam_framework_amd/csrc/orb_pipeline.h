@@ -15,6 +15,12 @@
 
 namespace msf {
 
+// Capacities.  A frame whose reference counts exceed one of them comes back with n_out = -1 (MSF_ERR_CAPACITY), in every
+// call form and whatever else the call holds; every other frame is exact (tests/orb_capacity.py restates them):
+//  * kKpCap: final key points of a frame;
+//  * per level, min(kS1Cap, full list): key points kept by retainBest(2N) (stage 1);
+//  * a dense CALL only (MSF_FLAG_FAST_DENSE, fewer than eight frames): per level, strict FAST maxima at fastThreshold
+//    inside the 31-px border > full list (OrbLevelInfo::cand_cap, w h / 8).  A streaming call never lists them all.
 constexpr int kOrbLevels = 8;
 constexpr int kKpCap = 2048;       // keypoints per frame (cv::ORB nfeatures = 500, + ties)
 constexpr int kOrbStages = 6;
@@ -42,7 +48,7 @@ struct OrbLevelInfo {
   long long pix_off;   // byte offset of this level inside a slot's pyramid blob (levels >= 1)
 };
 
-// per level: capacity of the PRIMARY candidate list (the output-sensitive pass: w h / 64, at least 4096; small levels keep
+// per level: capacity of the PRIMARY candidate list (the output-sensitive pass: w h / 64, at least kS1Cap; small levels keep
 // their full capacity) and its offset (entries) inside a work row's primary region.  (A struct of its own, passed to the
 // one kernel that needs it: inside OrbGeometry or OrbLevelInfo the extra members put the walker's copies into scratch.)
 struct OrbPrimLists {
@@ -57,11 +63,11 @@ struct OrbGeometry {
   int max_level_tiles;     // largest tile count of one level
   int cand_total;          // candidate entries of a frame at full capacity (dense calls: one such region per frame in the pool)
   int prim_total;          // candidate entries per work row (primary lists)
-  // r05: the candidate arrays are [work rows][prim_total] followed by a POOL of pool_entries entries.  The dense second
-  // pass of a (frame, level) first writes into the level's primary list (a smooth frame's dense list is short); only a
-  // level that overflows it takes a region of its full capacity from the pool (a bump allocation per call) and is redone
-  // once more.  A call that is dense altogether (MSF_FLAG_FAST_DENSE, fewer than eight frames) lays its frames'
-  // full-capacity regions over the pool.  Exhausted pool: MSF_ERR_CAPACITY for that frame, never a short list.
+  // The candidate arrays are [work rows][prim_total] followed by a POOL of pool_entries entries.  A streaming call lists
+  // into the primary lists only: the dense second pass of a (frame, level) counts the scores of its maxima, then lists
+  // them all into the level's primary list if they fit, else those at or above the retainBest(2N) cut -- the level's
+  // stage 1 (k_fast_redo) --, so no level needs room beyond its own.  A call that is dense altogether (MSF_FLAG_FAST_DENSE, fewer than eight frames)
+  // lays its frames' full-capacity regions over the pool (sized for that at init).
   long long pool_base;     // first pool entry
   unsigned pool_entries;
   int s1_total;            // stage-1 entries per slot
@@ -137,10 +143,11 @@ class OrbPipeline {
   uint32_t* d_cand_cnt_ = nullptr; // [slots][8]
   uint32_t* d_tau_ = nullptr;      // [2][slots][8] FAST score threshold used per (slot, level) | first estimate
   uint32_t* d_redo_ = nullptr;     // [1 + slots * 8] dense-pass queue: count, entries (frame * 8 + level)
-  uint32_t* d_cand_ = nullptr;     // [work rows][prim_total] + pool: key = y << 16 | x
+  uint32_t* d_redo_hist_ = nullptr;  // [work rows][8][256] dense pass: score histogram of a queued level's maxima (kept zeroed)
+  uint32_t* d_redo_thr_ = nullptr;   // [work rows][8] dense pass: the level's retainBest(2N) cut (k_redo_thr)
+  uint32_t* d_cand_ = nullptr;     // [work rows][prim_total] + pool (dense calls): key = y << 16 | x
   uint8_t* d_cand_sc_ = nullptr;   // the same shape: FAST score
   uint2* d_cmap_ = nullptr;        // [work rows][8] where the list of (frame, level) lives: (first entry, capacity); reset per call
-  uint32_t* d_pool_cnt_ = nullptr; // pool entries handed out in the current call
   uint32_t* d_s1_cnt_ = nullptr;   // [slots][8]
   uint4* d_s1_ = nullptr;          // [slots][s1_total] (key, response bits, score, 0)
   // per feature SLOT (max_slots_): what a later match reads
@@ -169,6 +176,7 @@ class OrbPipeline {
   bool ev_ok_ = false, ev_extract_pending_ = false;
   FrameSrc last_src_{};
   bool last_fused_ = false;
+  bool last_dense_ = false;        // the last extraction was a dense call (no streaming pass, no dense-pass queue)
   hipError_t extract_range(const FrameSrc& src, int n, hipStream_t st, hipEvent_t* evs);
 };
 

@@ -318,20 +318,42 @@ def _adversarial_images(w, h):
 @pytest.mark.parametrize("name,img", _adversarial_images(640, 480), ids=["checker2", "dots4", "salt"])
 def test_adversarial_density_is_exact_or_loud(name, img):
     """Fixed-capacity device lists may overflow on pathological inputs; then the call must fail loudly
-    (MSF_ERR_CAPACITY), otherwise the result must still be bit-exact."""
+    (MSF_ERR_CAPACITY) -- and only if the oracle's own counts exceed a documented cap (tests/orb_capacity.py) --,
+    otherwise the result must be bit-exact.  The same frames as an 8-pair batch (the streaming pass) likewise."""
     from mono_slam_framework_amd.matcher import MsfError
+    from tests import orb_capacity as oc
     img2 = np.roll(img, (3, 5), (0, 1))
+    over = [oc.capacity(x) for x in (img, img2)]
+    loud = any(c.loud for c in over)
     fm = _matcher(640, 480)
     orc = oracle_orb.FeatureMatcherOracle(0.8)
     exp = orc.MatchFrames(img, img2)
     try:
         got = fm.MatchFrames(img, img2)
+        assert not loud, "over caps %s, but the call returned a list" % over
+        np.testing.assert_array_equal(got, exp)
+        (k1, _), (k2, _) = orc.extract_both(img, img2)
+        assert len(fm.keypoints(0)) == len(k1) and len(fm.keypoints(1)) == len(k2)
     except MsfError as e:
-        assert e.code == -4
-        return
-    np.testing.assert_array_equal(got, exp)
-    (k1, _), (k2, _) = orc.extract_both(img, img2)
-    assert len(fm.keypoints(0)) == len(k1) and len(fm.keypoints(1)) == len(k2)
+        assert e.code == -4 and loud, "loud (%s) within caps: %s" % (e, over)
+    # batch form: the three images against their shifted copies, mixed with synthetic pairs
+    from mono_slam_framework_amd import _lib
+    from mono_slam_framework_amd.matcher import FeatureMatcher
+    imgs = [x for _, x in _adversarial_images(640, 480)]
+    A, B = synth.synth_batch(60, 5, 640, 480)
+    fa = [imgs[0], A[0], imgs[1], A[1], A[2], imgs[2], A[3], A[4]]
+    fb = [np.roll(imgs[0], (3, 5), (0, 1)), B[0], np.roll(imgs[1], (3, 5), (0, 1)), B[1], B[2],
+          np.roll(imgs[2], (3, 5), (0, 1)), B[3], B[4]]
+    fmb = FeatureMatcher(0.8, 640, 480, max_batch_pairs=8, flags=_lib.MSF_FLAG_NO_FRAME_CACHE)
+    num, lists = fmb.match_batch_raw(fa, fb, cap=4096)
+    for i in range(8):
+        caps = [oc.capacity(fa[i]), oc.capacity(fb[i])]
+        if any(c.loud for c in caps):
+            assert num[i] == -1, (i, caps)
+        else:
+            assert num[i] >= 0, (i, caps)
+            np.testing.assert_array_equal(lists[i], orc.MatchFrames(fa[i], fb[i]), err_msg="batch pair %d" % i)
+    fmb.close()
 
 
 def test_chunked_match_path():
@@ -485,9 +507,8 @@ def test_refined_fast_threshold_equals_unrefined_and_survives_an_overshooting_es
     assert (tau_two[:, :3, 0] > tau_one[:, :3, 0]).mean() > 0.5
     assert (tau_two[:, :, 0] == tau_two[:, :, 1]).all()                    # nothing redone
     # an absurd prediction margin (5 % of the needed density: thresholds far too high) only costs dense passes
-    # (these two settings send most levels of the batch through the dense pass: the pool of full-capacity candidate
-    # lists, sized for an eighth of them, is made large enough for all -- r05, orb_pipeline.h)
-    monkeypatch.setenv("MSF_ORB_POOL_ENTRIES", str(1 << 30))
+    # (this and the margin below send most levels of the batch through the dense pass, with the default configuration:
+    # a redone level lists its stage 1 into its own primary list, orb_pipeline.h)
     monkeypatch.setenv("MSF_ORB_TAU_PREDICT", "5")
     wildp = FeatureMatcher(0.7, w, h, max_batch_pairs=n, flags=fl)
     got_p = wildp.match_batch(list(A), list(B), cap=1024)
@@ -508,7 +529,6 @@ def test_refined_fast_threshold_equals_unrefined_and_survives_an_overshooting_es
     for r, g in zip(ref, got2):
         np.testing.assert_array_equal(r, g)
     monkeypatch.delenv("MSF_ORB_TAU2_MARGIN_PCT")
-    monkeypatch.delenv("MSF_ORB_POOL_ENTRIES")
     for env in ({"MSF_ORB_WALK_PER_LEVEL": "1"}, {"MSF_ORB_UNFUSED": "1"},
                 {"MSF_ORB_WALK_PER_LEVEL": "1", "MSF_ORB_TAU_PREDICT": "0"}):
         for k, v in env.items():
@@ -681,33 +701,25 @@ def test_two_walker_grids_at_once():
 
 
 @pytest.mark.gpu
-def test_candidate_pool_exhaustion_is_loud_and_the_footprint_is_what_the_header_says(monkeypatch):
-    """r05: a (frame, level) keeps a small primary candidate list (w h / 64 entries) and takes a full-capacity region of a
-    shared pool only when it goes through the dense second pass (orb_pipeline.h).  (1) With the pool cut to nothing
-    (MSF_ORB_POOL_ENTRIES=0) and a first threshold no level can satisfy (MSF_ORB_FAST_TAU=254: every level needs the dense
-    pass) the pairs that find no region report n_out = -1 / MSF_ERR_CAPACITY -- never a short list; with the default pool the same batch is
-    the oracle's (test_fast_threshold_fallback_path).  (2) A handle for 1024 pairs of 1280 x 720 takes less than the 8 GB
-    include/msf_abi.h states (r04: 10.4 GB, r03: 20 GB)."""
+def test_forced_dense_pass_needs_no_pool_and_the_footprint_is_what_the_header_says(monkeypatch):
+    """A (frame, level) keeps a small primary candidate list (w h / 64 entries, at least kS1Cap); the pool of
+    full-capacity lists behind them serves dense CALLS only (orb_pipeline.h).  (1) With a first threshold no level can
+    satisfy (MSF_ORB_FAST_TAU=254: every level of every frame takes the dense second pass) a streaming batch, which gets
+    no pool at all, is the oracle's pair for pair: the dense pass lists each level's stage 1 into its own primary list.
+    (2) A handle for 1024 pairs of 1280 x 720 takes less than the 8 GB include/msf_abi.h states (r04: 10.4 GB, r03: 20 GB)."""
     import torch
     from mono_slam_framework_amd import _lib
     from mono_slam_framework_amd.matcher import FeatureMatcher
     n, w, h = 8, 640, 480
     A, B = synth.synth_batch(12500, n, w, h, mode=0)
     monkeypatch.setenv("MSF_ORB_FAST_TAU", "254")
-    monkeypatch.setenv("MSF_ORB_POOL_ENTRIES", "0")
     fm = FeatureMatcher(0.7, w, h, max_batch_pairs=n, flags=_lib.MSF_FLAG_NO_FRAME_CACHE)
     num, lists = fm.match_batch_raw(list(A), list(B), cap=1024)
-    # (the pool keeps the regions dense CALLS need -- 7 frames' worth here -- and the overflowing levels race for them:
-    # which frames lose is not determined, that most do is; a pair that got its regions must be the oracle's)
-    assert (num == -1).sum() >= n // 2, num
-    for i in np.nonzero(num >= 0)[0]:
-        np.testing.assert_array_equal(lists[i], oracle_orb.FeatureMatcherOracle(0.7).MatchFrames(A[i], B[i]))
-    fm.close()
-    monkeypatch.delenv("MSF_ORB_POOL_ENTRIES")
-    fm = FeatureMatcher(0.7, w, h, max_batch_pairs=n, flags=_lib.MSF_FLAG_NO_FRAME_CACHE)
-    num, lists = fm.match_batch_raw(list(A), list(B), cap=1024)
-    assert (num >= 0).all()
-    np.testing.assert_array_equal(lists[3], oracle_orb.FeatureMatcherOracle(0.7).MatchFrames(A[3], B[3]))
+    assert (num >= 0).all(), num
+    orc = oracle_orb.FeatureMatcherOracle(0.7)
+    for i in range(n):
+        np.testing.assert_array_equal(lists[i], orc.MatchFrames(A[i], B[i]), err_msg="pair %d" % i)
+    assert all((fm.fast_tau(s)[:, 0] == 20).all() for s in range(2 * n))
     fm.close()
     monkeypatch.delenv("MSF_ORB_FAST_TAU")
     torch.cuda.synchronize()
