@@ -338,6 +338,14 @@ typedef enum msf_debug_what {
 /* copies to host; *n_bytes = bytes available (may exceed cap_bytes, then only cap_bytes are written) */
 int msf_debug_get(msf_handle* h, int32_t what, int32_t slot, int32_t level,
                   void* host_out, size_t cap_bytes, size_t* n_bytes);
+/* LoFTR: the matching head alone (similarity, dual soft-max, '> threshold', row-major list) on coarse features the caller
+ * supplies.  d_feat0 / d_feat1: device float [n_pairs][1200][32], post-transformer and unscaled (the layout of
+ * MSF_DBG_LOFTR_FEAT).  Runs the head exactly as a match call on this handle would: its threshold, MSF_FLAG_LOFTR_F32 and
+ * the head switches read at msf_create; with MSF_FLAG_KEEP_DEBUG pair 0's confidence matrix and features are kept for
+ * msf_debug_get.  d_out / d_n_out as msf_match_batch_device.  MSF_ERR_INVALID_ARG for an ORB handle, n_pairs above
+ * max_batch_pairs, features or d_out not 16-byte aligned, d_n_out not 4-byte aligned.  Not timed by msf_stage_times. */
+int msf_debug_loftr_head(msf_handle* h, int32_t n_pairs, const float* d_feat0, const float* d_feat1,
+                         msf_match* d_out, int32_t cap_per_pair, int32_t* d_n_out, void* stream);
 
 /* per-stage device time, measured with HIP events on the launch stream (needs MSF_FLAG_PROFILE): the SUM over the batch
  * calls since the previous query -- queried after every call it is that call's times; a caller that enqueues many calls

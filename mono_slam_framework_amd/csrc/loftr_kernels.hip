@@ -3455,6 +3455,23 @@ __global__ __launch_bounds__(256) void k_scale_feats(const float* __restrict__ i
   }
 }
 
+// the split path's head inputs from unscaled features, as k_attn_update_x forms them in the last two encoder blocks
+// (times the rounded reciprocal, not k_scale_feats' division): only msf_debug_loftr_head launches it
+__global__ __launch_bounds__(256) void k_head_inputs(const float* __restrict__ in, float* __restrict__ out, long long n,
+                                                     __bf16* __restrict__ planes, long long ts) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float v = in[i] * kInvSqrtDM;
+  out[i] = v;
+  const long long pair = i / ts, e = i - pair * ts;
+  const __bf16 h = (__bf16)v;
+  const float e1 = v - (float)h;
+  const __bf16 m = (__bf16)e1;
+  const __bf16 l = (__bf16)(e1 - (float)m);
+  __bf16* dst = planes + pair * 3 * ts + e;
+  dst[0] = h; dst[ts] = m; dst[2 * ts] = l;
+}
+
 // x / 0.1f, correctly rounded, in three instructions: 10.0f is the correctly rounded reciprocal of 0.1f, so one
 // Newton step on the exact fma residual gives RN(x / 0.1f) (Markstein); checked bit for bit against IEEE division on
 // 1.2e8 values across the magnitudes that occur.  The generic correctly rounded division costs ~10 instructions, four
@@ -5024,8 +5041,39 @@ void run_backbone(LoftrPipeline::Impl& P, const uint8_t* srcA, int nA, float* to
 hipError_t LoftrPipeline::transformer_and_head(int n_pairs, float threshold, msf_match* d_out, int cap,
                                                int32_t* d_n_out, hipStream_t st) {
   Impl& P = *p_;
-  const long long ts = (long long)NTOK * DM;
   hipEvent_t* ev = P.ev_ok ? P.ev_cur_set() : nullptr;      // the set match() / match_slots() began
+  transformer(n_pairs, st);
+  if (ev) hipEventRecord(ev[2], st);
+  head(n_pairs, threshold, d_out, cap, d_n_out, st);
+  if (ev) { hipEventRecord(ev[3], st); P.ev_set_rec[P.ev_cur] = true; }
+  return hipGetLastError();
+}
+
+// msf_debug_loftr_head: the caller's features take the place of the transformer's output (tok[0] / tok[1]); on the split
+// path the head's inputs are formed as the last two encoder blocks form them (k_attn_update_x: x * kInvSqrtDM and its
+// three bf16 planes), on the exact-f32 path head() forms them itself (k_scale_feats: x / 5.656854f)
+hipError_t LoftrPipeline::head_only(int n_pairs, const float* d_f0, const float* d_f1, float threshold, msf_match* d_out,
+                                    int cap, int32_t* d_n_out, hipStream_t st) {
+  if (!p_) return hipErrorNotInitialized;
+  Impl& P = *p_;
+  if (n_pairs > P.max_pairs) return hipErrorInvalidValue;
+  if (n_pairs <= 0) return hipSuccess;
+  const long long ts = (long long)NTOK * DM, n = (long long)n_pairs * ts;
+  hipMemcpyAsync(P.tok[0], d_f0, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st);
+  hipMemcpyAsync(P.tok[1], d_f1, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st);
+  if (P.split_bf16) {
+    const dim3 grid((unsigned)((n + 255) / 256));
+    hipLaunchKernelGGL(k_head_inputs, grid, dim3(256), 0, st, P.tok[0], P.fsc, n, P.fsp, ts);
+    hipLaunchKernelGGL(k_head_inputs, grid, dim3(256), 0, st, P.tok[1], P.fsc + (long long)P.max_pairs * ts, n,
+                       P.fsp + (long long)P.max_pairs * 3 * ts, ts);
+  }
+  head(n_pairs, threshold, d_out, cap, d_n_out, st);
+  return hipGetLastError();
+}
+
+void LoftrPipeline::transformer(int n_pairs, hipStream_t st) {
+  Impl& P = *p_;
+  const long long ts = (long long)NTOK * DM;
   // ---- 8 encoder blocks over all pairs: (x, source) -> dst   [self, self, cross, cross(updated feat0)] x 2
   const int n = n_pairs;
   float *f0 = P.tok[0], *f1 = P.tok[1], *t0 = P.tok[2], *t1 = P.tok[3];
@@ -5055,7 +5103,13 @@ hipError_t LoftrPipeline::transformer_and_head(int n_pairs, float threshold, msf
     hipLaunchKernelGGL(k_attn_kv, dim3(n), dim3(64 * kKvWaves), 0, st, seq[bi].s, ts, P.blk[bi], P.kv);
     hipLaunchKernelGGL(k_attn_update, dim3(upd_blocks, n), dim3(256), 0, st, seq[bi].x, ts, P.kv, P.blk[bi], seq[bi].o, ts);
   }
-  if (ev) hipEventRecord(ev[2], st);
+}
+
+void LoftrPipeline::head(int n_pairs, float threshold, msf_match* d_out, int cap, int32_t* d_n_out, hipStream_t st) {
+  Impl& P = *p_;
+  const long long ts = (long long)NTOK * DM;
+  const int n = n_pairs;
+  float *f0 = P.tok[0], *f1 = P.tok[1];
   // ---- matching head on (f0, f1)
   float* f0s = P.fsc;
   float* f1s = P.fsc + (long long)P.max_pairs * ts;
@@ -5128,8 +5182,6 @@ hipError_t LoftrPipeline::transformer_and_head(int n_pairs, float threshold, msf
     hipMemcpyAsync(P.feat_dbg + ts, f1, ts * sizeof(float), hipMemcpyDeviceToDevice, st);
     P.have_dbg = true;
   }
-  if (ev) { hipEventRecord(ev[3], st); P.ev_set_rec[P.ev_cur] = true; }
-  return hipGetLastError();
 }
 
 int LoftrPipeline::stage_times(const char** names, float* ms, int cap) {

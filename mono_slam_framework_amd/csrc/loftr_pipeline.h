@@ -31,6 +31,10 @@ class LoftrPipeline {
   // caller cannot reach the handle's private cache slots); 0: every slot of the pipeline
   hipError_t match_slots(int n_pairs, const int32_t* d_slot_a, const int32_t* d_slot_b, float threshold,
                          msf_match* d_out, int cap_per_pair, int32_t* d_n_out, hipStream_t st, int slot_limit = 0);
+  // the matching head alone on caller-supplied post-transformer features (unscaled, [n_pairs][1200][32] each): the same
+  // head inputs, kernels and debug copies as match(); not recorded in the stage-timing events (msf_debug_loftr_head)
+  hipError_t head_only(int n_pairs, const float* d_f0, const float* d_f1, float threshold, msf_match* d_out,
+                       int cap_per_pair, int32_t* d_n_out, hipStream_t st);
   int max_slots() const;
   int debug_get(int what, int slot, int level, void* host_out, size_t cap, size_t* n_bytes, std::string* err);
   int stage_times(const char** names, float* ms, int cap);
@@ -40,6 +44,10 @@ class LoftrPipeline {
  private:
   hipError_t transformer_and_head(int n_pairs, float threshold, msf_match* d_out, int cap_per_pair, int32_t* d_n_out,
                                   hipStream_t st);
+  // the 8 encoder blocks: final features in tok[0] / tok[1]; the split path also leaves the head's inputs (fsc, fsp)
+  void transformer(int n_pairs, hipStream_t st);
+  // similarity, dual soft-max, threshold, decode on tok[0] / tok[1] (+ fsc / fsp on the split path)
+  void head(int n_pairs, float threshold, msf_match* d_out, int cap_per_pair, int32_t* d_n_out, hipStream_t st);
   Impl* p_ = nullptr;
 };
 

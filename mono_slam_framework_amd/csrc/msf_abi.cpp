@@ -834,6 +834,28 @@ int msf_debug_get(msf_handle* h, int32_t what, int32_t slot, int32_t level, void
   }
 }
 
+int msf_debug_loftr_head(msf_handle* h, int32_t n_pairs, const float* d_feat0, const float* d_feat1,
+                         msf_match* d_out, int32_t cap_per_pair, int32_t* d_n_out, void* stream) {
+  try {
+    if (!h) return MSF_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->cfg.kind != MSF_KIND_LOFTR) return fail(h, MSF_ERR_INVALID_ARG, "msf_debug_loftr_head: not a LoFTR handle");
+    if (n_pairs < 0 || n_pairs > h->cfg.max_batch_pairs || !d_feat0 || !d_feat1 || !d_out || !d_n_out || cap_per_pair < 1)
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_debug_loftr_head: bad argument");
+    if ((((uintptr_t)d_feat0 | (uintptr_t)d_feat1 | (uintptr_t)d_out) & 15) || ((uintptr_t)d_n_out & 3))
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_debug_loftr_head: misaligned pointer");
+    hipError_t e = hipSetDevice(h->cfg.device);
+    if (e != hipSuccess) return hip_fail(h, "hipSetDevice", e);
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    e = h->loftr.head_only(n_pairs, d_feat0, d_feat1, h->cfg.threshold, d_out, cap_per_pair, d_n_out, st);
+    if (e != hipSuccess) return hip_fail(h, "loftr head", e);
+    if (!stream && (e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(h, "hipStreamSynchronize", e);
+    return MSF_OK;
+  } catch (...) {
+    return host_exception(h, "msf_debug_loftr_head");
+  }
+}
+
 int msf_stage_times(msf_handle* h, const char** names, float* ms, int32_t cap) {
   try {
     if (!h || !names || !ms || cap < 1) return 0;

@@ -289,6 +289,19 @@ class DNNFeatureMatcher(_Matcher):
     def coarse_features(self, pair=0):
         return self._debug(_lib.DBG_LOFTR_FEAT, pair, 0, np.float32, 2 * 1200 * 32 * 4).reshape(2, 1200, 32)
 
+    def head_device(self, d_f0, d_f1, d_out, d_n_out, stream=None):
+        """The matching head alone (msf_debug_loftr_head) on coarse features the caller supplies: d_f0 / d_f1 float32
+        CUDA tensors [n, 1200, 32], post-transformer and unscaled (coarse_features() layout); d_out int32 [n, cap, 4],
+        d_n_out int32 [n].  Asynchronous on `stream` (an int hipStream_t; None = handle stream + sync)."""
+        import torch
+        n = d_f0.shape[0]
+        for t, dt in ((d_f0, torch.float32), (d_f1, torch.float32), (d_out, torch.int32), (d_n_out, torch.int32)):
+            assert t.is_cuda and t.dtype == dt and t.is_contiguous()
+        assert tuple(d_f0.shape) == (n, 1200, 32) and d_f1.shape == d_f0.shape
+        assert d_out.dim() == 3 and d_out.shape[0] == n and d_out.shape[2] == 4 and tuple(d_n_out.shape) == (n,)
+        self._check(self._L.msf_debug_loftr_head(self._h, n, d_f0.data_ptr(), d_f1.data_ptr(), d_out.data_ptr(),
+                                                 d_out.shape[1], d_n_out.data_ptr(), stream))
+
     def backbone_activation(self, stage):
         """NCHW activation of the first frame of the last call after ResNet stage `stage` + 1 (MSF_FLAG_KEEP_DEBUG)"""
         shape = [(8, 240, 320), (16, 120, 160), (32, 60, 80), (32, 30, 40)][stage]
