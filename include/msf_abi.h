@@ -332,8 +332,10 @@ typedef enum msf_debug_what {
   MSF_DBG_WALK_MODE = 10,    /* ORB, int32 [2]: {1 if the handle launches the pyramid + FAST walker level by level (after a
                                 stalled one-launch walker, or MSF_ORB_WALK_PER_LEVEL=1), else 0; units of one-launch
                                 walkers that gave up a bounded wait since msf_create} -- see "Walker stall" below */
-  MSF_DBG_LOFTR_ACT = 9      /* float NCHW activation of the first frame of the last backbone pass after ResNet stage
+  MSF_DBG_LOFTR_ACT = 9,     /* float NCHW activation of the first frame of the last backbone pass after ResNet stage
                                 `level` + 1: [8][240][320], [16][120][160], [32][60][80], [32][30][40] (level 0..3) */
+  MSF_DBG_LOFTR_TOK = 11     /* float [2][1200][32] tokens of pair 0 before the transformer (backbone + positional
+                                encoding) of the last match call; MSF_FLAG_KEEP_DEBUG handles only */
 } msf_debug_what;
 /* copies to host; *n_bytes = bytes available (may exceed cap_bytes, then only cap_bytes are written) */
 int msf_debug_get(msf_handle* h, int32_t what, int32_t slot, int32_t level,
@@ -346,6 +348,17 @@ int msf_debug_get(msf_handle* h, int32_t what, int32_t slot, int32_t level,
  * max_batch_pairs, features or d_out not 16-byte aligned, d_n_out not 4-byte aligned.  Not timed by msf_stage_times. */
 int msf_debug_loftr_head(msf_handle* h, int32_t n_pairs, const float* d_feat0, const float* d_feat1,
                          msf_match* d_out, int32_t cap_per_pair, int32_t* d_n_out, void* stream);
+
+/* LoFTR: encoder blocks [first_block, first_block + n_blocks) of the coarse transformer alone, on sequences the caller
+ * supplies.  Block b updates sequence b % 2 (0: feat0, 1: feat1) from itself (b % 4 < 2, self-attention) or from the
+ * other sequence's current value (cross-attention).  d_in0 / d_in1: device float [n_pairs][1200][32], the two sequences
+ * before block first_block (the layout of MSF_DBG_LOFTR_TOK / MSF_DBG_LOFTR_FEAT); d_out0 / d_out1 receive them after
+ * the range (a sequence no block of the range updates is copied through).  The kernels, MSF_FLAG_LOFTR_F32 and the
+ * switches read at msf_create are those of a match call on this handle; two blocks share a launch only when both are in
+ * the range.  MSF_ERR_INVALID_ARG for an ORB handle, n_pairs outside [0, max_batch_pairs], first_block < 0,
+ * n_blocks < 1, first_block + n_blocks > 8, a pointer not 16-byte aligned.  Not timed by msf_stage_times. */
+int msf_debug_loftr_transformer(msf_handle* h, int32_t n_pairs, int32_t first_block, int32_t n_blocks,
+                                const float* d_in0, const float* d_in1, float* d_out0, float* d_out1, void* stream);
 
 /* per-stage device time, measured with HIP events on the launch stream (needs MSF_FLAG_PROFILE): the SUM over the batch
  * calls since the previous query -- queried after every call it is that call's times; a caller that enqueues many calls

@@ -4242,6 +4242,7 @@ struct LoftrPipeline::Impl {
   bool keep_debug = false;   // MSF_FLAG_KEEP_DEBUG: pair 0's confidence matrix + features for the parity tests
   float* conf_dbg = nullptr; // [1200][1200]
   float* feat_dbg = nullptr; // [2][1200][32]
+  float* tok_dbg = nullptr;  // [2][1200][32] pair 0's tokens before the transformer (keep_debug only)
   float* act_dbg[4] = {nullptr, nullptr, nullptr, nullptr};   // frame A of pair 0 after layer1..4: [8][240][320], [16][120][160], [32][60][80], [32][30][40]
   bool act_split[4] = {false, false, false, false};           // ... kept in the streaming kernels' split-pixel format (debug_get converts)
   int dbg_pair = 0;
@@ -4679,6 +4680,7 @@ std::string LoftrPipeline::init(const char* weights_path, int max_pairs, bool pr
   if (keep_debug) {
     const size_t act_elems[4] = {8u * 240 * 320, 16u * 120 * 160, 32u * 60 * 80, 32u * 30 * 40};
     for (int l = 0; l < 4; l++) LF_TRY(dalloc(&P.act_dbg[l], act_elems[l]));
+    LF_TRY(dalloc(&P.tok_dbg, (size_t)2 * NTOK * DM));
   }
   if (profile) {
     P.ev.resize(4 * Impl::kEvRing);
@@ -5042,7 +5044,12 @@ hipError_t LoftrPipeline::transformer_and_head(int n_pairs, float threshold, msf
                                                int32_t* d_n_out, hipStream_t st) {
   Impl& P = *p_;
   hipEvent_t* ev = P.ev_ok ? P.ev_cur_set() : nullptr;      // the set match() / match_slots() began
-  transformer(n_pairs, st);
+  if (P.tok_dbg) {
+    const long long ts = (long long)NTOK * DM;
+    hipMemcpyAsync(P.tok_dbg, P.tok[0], ts * sizeof(float), hipMemcpyDeviceToDevice, st);
+    hipMemcpyAsync(P.tok_dbg + ts, P.tok[1], ts * sizeof(float), hipMemcpyDeviceToDevice, st);
+  }
+  transformer(n_pairs, 0, 8, st);
   if (ev) hipEventRecord(ev[2], st);
   head(n_pairs, threshold, d_out, cap, d_n_out, st);
   if (ev) { hipEventRecord(ev[3], st); P.ev_set_rec[P.ev_cur] = true; }
@@ -5071,7 +5078,32 @@ hipError_t LoftrPipeline::head_only(int n_pairs, const float* d_f0, const float*
   return hipGetLastError();
 }
 
-void LoftrPipeline::transformer(int n_pairs, hipStream_t st) {
+// Where sequence `side` (0: feat0, 1: feat1) is before encoder block `bi` (0..8): block bi writes sequence bi % 2, and each
+// write alternates between tok[side] and tok[side + 2] (the table in transformer()).
+static float* seq_buffer(LoftrPipeline::Impl& P, int side, int bi) {
+  const int writes = side == 0 ? (bi + 1) / 2 : bi / 2;
+  return P.tok[side + 2 * (writes & 1)];
+}
+
+// msf_debug_loftr_transformer: the caller's sequences go where block `first` reads them, blocks [first, first + n_blocks)
+// run as transformer() runs them, and the two sequences are copied out from where the last block of the range left them
+hipError_t LoftrPipeline::transformer_only(int n_pairs, int first, int n_blocks, const float* d_in0, const float* d_in1,
+                                           float* d_out0, float* d_out1, hipStream_t st) {
+  if (!p_) return hipErrorNotInitialized;
+  Impl& P = *p_;
+  if (n_pairs > P.max_pairs || first < 0 || n_blocks < 1 || first + n_blocks > 8) return hipErrorInvalidValue;
+  if (n_pairs <= 0) return hipSuccess;
+  const size_t bytes = (size_t)n_pairs * NTOK * DM * sizeof(float);
+  const int end = first + n_blocks;
+  hipMemcpyAsync(seq_buffer(P, 0, first), d_in0, bytes, hipMemcpyDeviceToDevice, st);
+  hipMemcpyAsync(seq_buffer(P, 1, first), d_in1, bytes, hipMemcpyDeviceToDevice, st);
+  transformer(n_pairs, first, n_blocks, st);
+  hipMemcpyAsync(d_out0, seq_buffer(P, 0, end), bytes, hipMemcpyDeviceToDevice, st);
+  hipMemcpyAsync(d_out1, seq_buffer(P, 1, end), bytes, hipMemcpyDeviceToDevice, st);
+  return hipGetLastError();
+}
+
+void LoftrPipeline::transformer(int n_pairs, int first, int n_blocks, hipStream_t st) {
   Impl& P = *p_;
   const long long ts = (long long)NTOK * DM;
   // ---- 8 encoder blocks over all pairs: (x, source) -> dst   [self, self, cross, cross(updated feat0)] x 2
@@ -5080,11 +5112,13 @@ void LoftrPipeline::transformer(int n_pairs, hipStream_t st) {
   struct { const float* x; const float* s; float* o; } seq[8] = {
       {f0, f0, t0}, {f1, f1, t1}, {t0, t1, f0}, {t1, f0, f1}, {f0, f0, t0}, {f1, f1, t1}, {t0, t1, f0}, {t1, f0, f1}};
   const int upd_blocks = (NTOK / 16 + 4 * kUpdTilesPerWave - 1) / (4 * kUpdTilesPerWave);
-  for (int bi = 0; bi < 8; bi++) {
+  const int end = first + n_blocks;
+  for (int bi = first; bi < end; bi++) {
     if (P.split_bf16) {
       // the two self-attention blocks of a layer pair (0 | 1, 4 | 5) read and write disjoint sequences: ONE launch of each
-      // kernel for both (12 launches per call instead of 16; the second block's KV goes to the second half of P.kv)
-      const bool pairup = (bi & 3) == 0 && P.attn_pair;
+      // kernel for both (12 launches per call instead of 16; the second block's KV goes to the second half of P.kv) --
+      // when both blocks are in the range
+      const bool pairup = (bi & 3) == 0 && bi + 1 < end && P.attn_pair;
       const int bj = pairup ? bi + 1 : bi;
       float* kv2 = P.kv + (long long)P.max_pairs * (DM * DM + DM);
       hipLaunchKernelGGL(k_attn_kv_x, dim3(pairup ? 2 * n : n), dim3(64 * kKvWaves), 0, st, seq[bi].s, ts, P.blk[bi], P.kv, n,
@@ -5209,6 +5243,7 @@ int LoftrPipeline::debug_get(int what, int slot, int level, void* host_out, size
   size_t bytes = 0;
   if (what == MSF_DBG_LOFTR_CONF) { src = p_->conf_dbg; bytes = (size_t)NTOK * NTOK * 4; }
   else if (what == MSF_DBG_LOFTR_FEAT) { src = p_->feat_dbg; bytes = (size_t)2 * NTOK * DM * 4; }
+  else if (what == MSF_DBG_LOFTR_TOK && p_->tok_dbg) { src = p_->tok_dbg; bytes = (size_t)2 * NTOK * DM * 4; }
   else if (what == MSF_DBG_LOFTR_ACT && level >= 0 && level < 4 && p_->act_dbg[level]) {
     const size_t act_elems[4] = {8u * 240 * 320, 16u * 120 * 160, 32u * 60 * 80, 32u * 30 * 40};
     src = p_->act_dbg[level];

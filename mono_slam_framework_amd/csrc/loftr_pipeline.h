@@ -35,6 +35,11 @@ class LoftrPipeline {
   // head inputs, kernels and debug copies as match(); not recorded in the stage-timing events (msf_debug_loftr_head)
   hipError_t head_only(int n_pairs, const float* d_f0, const float* d_f1, float threshold, msf_match* d_out,
                        int cap_per_pair, int32_t* d_n_out, hipStream_t st);
+  // encoder blocks [first, first + n_blocks) alone (msf_debug_loftr_transformer): d_in0 / d_in1 are the two sequences
+  // before block `first`, d_out0 / d_out1 receive them after the range ([n_pairs][1200][32] each); the same kernels and
+  // arguments as match() (a layer pair's self-attention blocks share a launch when both are in the range); not timed
+  hipError_t transformer_only(int n_pairs, int first, int n_blocks, const float* d_in0, const float* d_in1, float* d_out0,
+                              float* d_out1, hipStream_t st);
   int max_slots() const;
   int debug_get(int what, int slot, int level, void* host_out, size_t cap, size_t* n_bytes, std::string* err);
   int stage_times(const char** names, float* ms, int cap);
@@ -44,8 +49,10 @@ class LoftrPipeline {
  private:
   hipError_t transformer_and_head(int n_pairs, float threshold, msf_match* d_out, int cap_per_pair, int32_t* d_n_out,
                                   hipStream_t st);
-  // the 8 encoder blocks: final features in tok[0] / tok[1]; the split path also leaves the head's inputs (fsc, fsp)
-  void transformer(int n_pairs, hipStream_t st);
+  // encoder blocks [first, first + n_blocks): block bi updates sequence bi % 2 from itself (bi % 4 < 2) or from the other
+  // sequence; the whole range [0, 8) leaves the final features in tok[0] / tok[1], and the split path's blocks 6 and 7
+  // also leave the head's inputs (fsc, fsp)
+  void transformer(int n_pairs, int first, int n_blocks, hipStream_t st);
   // similarity, dual soft-max, threshold, decode on tok[0] / tok[1] (+ fsc / fsp on the split path)
   void head(int n_pairs, float threshold, msf_match* d_out, int cap_per_pair, int32_t* d_n_out, hipStream_t st);
   Impl* p_ = nullptr;

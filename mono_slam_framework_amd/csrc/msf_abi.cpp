@@ -856,6 +856,29 @@ int msf_debug_loftr_head(msf_handle* h, int32_t n_pairs, const float* d_feat0, c
   }
 }
 
+int msf_debug_loftr_transformer(msf_handle* h, int32_t n_pairs, int32_t first_block, int32_t n_blocks,
+                                const float* d_in0, const float* d_in1, float* d_out0, float* d_out1, void* stream) {
+  try {
+    if (!h) return MSF_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->cfg.kind != MSF_KIND_LOFTR) return fail(h, MSF_ERR_INVALID_ARG, "msf_debug_loftr_transformer: not a LoFTR handle");
+    if (n_pairs < 0 || n_pairs > h->cfg.max_batch_pairs || first_block < 0 || n_blocks < 1 || first_block + n_blocks > 8 ||
+        !d_in0 || !d_in1 || !d_out0 || !d_out1)
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_debug_loftr_transformer: bad argument");
+    if (((uintptr_t)d_in0 | (uintptr_t)d_in1 | (uintptr_t)d_out0 | (uintptr_t)d_out1) & 15)
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_debug_loftr_transformer: misaligned pointer");
+    hipError_t e = hipSetDevice(h->cfg.device);
+    if (e != hipSuccess) return hip_fail(h, "hipSetDevice", e);
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    e = h->loftr.transformer_only(n_pairs, first_block, n_blocks, d_in0, d_in1, d_out0, d_out1, st);
+    if (e != hipSuccess) return hip_fail(h, "loftr transformer", e);
+    if (!stream && (e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(h, "hipStreamSynchronize", e);
+    return MSF_OK;
+  } catch (...) {
+    return host_exception(h, "msf_debug_loftr_transformer");
+  }
+}
+
 int msf_stage_times(msf_handle* h, const char** names, float* ms, int32_t cap) {
   try {
     if (!h || !names || !ms || cap < 1) return 0;

@@ -289,6 +289,21 @@ class DNNFeatureMatcher(_Matcher):
     def coarse_features(self, pair=0):
         return self._debug(_lib.DBG_LOFTR_FEAT, pair, 0, np.float32, 2 * 1200 * 32 * 4).reshape(2, 1200, 32)
 
+    def backbone_tokens(self, pair=0):
+        """pair 0's tokens before the transformer (backbone + positional encoding) of the last match call: [2][1200][32]"""
+        return self._debug(_lib.DBG_LOFTR_TOK, pair, 0, np.float32, 2 * 1200 * 32 * 4).reshape(2, 1200, 32)
+
+    def transformer_device(self, d_in0, d_in1, d_out0, d_out1, first=0, n=8, stream=None):
+        """Encoder blocks [first, first + n) alone (msf_debug_loftr_transformer): d_in0 / d_in1 float32 CUDA tensors
+        [p, 1200, 32], the two sequences before block `first`; d_out0 / d_out1 the same shape, written with the two
+        sequences after the range.  Asynchronous on `stream` (an int hipStream_t; None = handle stream + sync)."""
+        import torch
+        p = d_in0.shape[0]
+        for t in (d_in0, d_in1, d_out0, d_out1):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (p, 1200, 32)
+        self._check(self._L.msf_debug_loftr_transformer(self._h, p, first, n, d_in0.data_ptr(), d_in1.data_ptr(),
+                                                        d_out0.data_ptr(), d_out1.data_ptr(), stream))
+
     def head_device(self, d_f0, d_f1, d_out, d_n_out, stream=None):
         """The matching head alone (msf_debug_loftr_head) on coarse features the caller supplies: d_f0 / d_f1 float32
         CUDA tensors [n, 1200, 32], post-transformer and unscaled (coarse_features() layout); d_out int32 [n, cap, 4],
