@@ -206,7 +206,8 @@ int msf_store_frame(msf_handle* h, int32_t slot, const msf_image* img);
 int msf_match_one_to_many(msf_handle* h, int32_t query_slot, int32_t n, const int32_t* slots, int32_t* num_matches,
                           int32_t* num_mp, msf_match* out, int32_t cap_per_pair);
 
-/* "next" row 4 of SURVEY.md 8f: Initializer::CheckHomography / CheckFundamental (slam_pipeline/src/Initializer.cc:
+/* "next" row 4 of SURVEY.md 8f, the scorer alone (for callers that bring their own hypotheses; msf_find_models below
+ * makes them on the device as well): Initializer::CheckHomography / CheckFundamental (slam_pipeline/src/Initializer.cc:
  * 322-405, 407-487) for all n_hyp RANSAC hypotheses of FindHomography / FindFundamental (:152-199, :201-245) at once.
  * m21: [n_hyp][9] row-major H21 (or F21); m12: [n_hyp][9] H12 = H21^-1 (homography only, else NULL); matches: the
  * MatchFramesResult the Initializer was built from (mvKeys1/2, Initializer.cc:79-86); all HOST pointers.
@@ -217,6 +218,60 @@ int msf_match_one_to_many(msf_handle* h, int32_t query_slot, int32_t n, const in
 int msf_check_hypotheses(msf_handle* h, int32_t model, int32_t n_hyp, const float* m21, const float* m12,
                          int32_t n_matches, const msf_match* matches, float sigma, float* scores, int32_t* best,
                          uint8_t* best_inliers);
+
+/* "next" row 4, completed: FindHomography + FindFundamental of one Initializer::Initialize call (Initializer.cc:152-245)
+ * with the hypotheses made on the device too -- Normalize (:760-804), ComputeH21 / ComputeF21 (:246-320: the null vector
+ * of the 16 x 9 / 8 x 9 DLT matrix by a one-sided Jacobi SVD in f32, F's rank-2 projection), the denormalisation
+ * H21 = T2^-1 Hn T1 / F21 = T2' Fn T1 and H12 = H21^-1 (cofactors and determinant in f64, rounded once, as cv::Mat::inv) --
+ * fused with the scoring of msf_check_hypotheses: scores, *best and best_inliers are bit for bit what
+ * msf_check_hypotheses returns for the m21 / m12 reported here.  T1, T2 and the normalised points are bit-identical to the
+ * reference's sequential f32 loops; a null vector is defined up to sign and conditioning, not up to rounding: it is within
+ * 16 eps s1 / (s8 - s9) of a float64 SVD's (tests/test_ransac_gpu.py).  A non-finite normalisation (all x equal: infinite
+ * scale) gives NaN matrices and NaN scores, which are never kept.
+ * One result per model.  All pointers optional except best (and scores when n_hyp > 0); per hypothesis row-major [9]:
+ *   m21 [n_hyp][9] H21 / F21;  m12 [n_hyp][9] H12 (homography only);  fn [n_hyp][9] the rank-2 Fn in normalised
+ *   coordinates (fundamental only);  null_vec [n_hyp][9] the unit singular vector before rank-2 projection and
+ *   denormalisation (Hn / Fpre; for tests and callers that refine);  scores [n_hyp];  *best = the kept hypothesis or -1;
+ *   best_inliers [n_matches] its vbMatchesInliers (all 0 if none);  T1, T2 [9].
+ * msf_find_models: HOST pointers; sets [n_hyp][8] = mvSets, match indices (:99-120).  MSF_ERR_INVALID_ARG for
+ * n_matches > 8192, n_hyp > 0 with n_matches < 8 (the reference would draw from an empty range), an index outside
+ * [0, n_matches), a missing required pointer or a wrong struct_size.  n_hyp == 0: best = -1, all-false inliers.
+ * Works on handles of either kind. */
+typedef struct msf_ransac_result {
+  uint32_t struct_size; /* sizeof(msf_ransac_result) */
+  uint32_t reserved;    /* 0 */
+  float* m21;
+  float* m12;
+  float* fn;
+  float* null_vec;
+  float* scores;
+  int32_t* best;
+  uint8_t* best_inliers;
+  float* T1;
+  float* T2;
+} msf_ransac_result;
+int msf_find_models(msf_handle* h, int32_t n_matches, const msf_match* matches, int32_t n_hyp, const int32_t* sets,
+                    float sigma, msf_ransac_result* homography, msf_ransac_result* fundamental);
+/* The same for n_lists <= 65535 match lists in DEVICE memory, as msf_match_batch_device leaves them: list l is
+ * d_matches + l * cap_per_pair, its length min(d_n_out[l], cap_per_pair).  The sets are drawn on the device by the
+ * reference's procedure (:106-120) with a counter-based generator keyed by (seed, list, iteration, draw) -- documented in
+ * csrc/ransac_kernels.hip; the reference seeds std::mt19937 from std::random_device, so there is no sequence to match --
+ * and reported in out->sets [n_lists][n_hyp][8] (optional): list l replayed through msf_find_models with its sets gives
+ * bit-identical results, and a list's results do not depend on the other lists of the call.  All pointers of `out` are
+ * DEVICE pointers with a leading [n_lists] dimension (best [n_lists], best_inliers [n_lists][cap_per_pair], false beyond
+ * the list, T1 [n_lists][9], ...), optional as above.  A list shorter than 8 (n_out = -1 included) or longer than 8192
+ * gets best = -1, all-false inliers and zero scores; its matrices and sets are not meaningful.  n_hyp <= 2^20.
+ * Asynchronous on `stream` like the other *_device calls. */
+typedef struct msf_ransac_batch {
+  uint32_t struct_size; /* sizeof(msf_ransac_batch) */
+  uint32_t reserved;    /* 0 */
+  int32_t* sets;
+  msf_ransac_result homography;
+  msf_ransac_result fundamental;
+} msf_ransac_batch;
+int msf_find_models_device(msf_handle* h, int32_t n_lists, const msf_match* d_matches, int32_t cap_per_pair,
+                           const int32_t* d_n_out, int32_t n_hyp, uint64_t seed, float sigma,
+                           msf_ransac_batch* out, void* stream);
 
 /* Tracking::CreateCurrentMatchImage (slam_pipeline/src/Tracking.cc:899-940): out_rgb [H][2*W][3] (rows out_stride
  * bytes apart, HOST) = the two gray frames side by side as RGB with a filled radius-3 circle on every match end point:

@@ -36,6 +36,7 @@ ABI_SYMBOLS = ["msf_abi_version", "msf_default_config", "msf_create", "msf_destr
                "msf_debug_loftr_head", "msf_debug_loftr_transformer",
                "msf_stage_times", "msf_set_mappoints", "msf_count_mappoint_matches_device",
                "msf_store_frame", "msf_match_one_to_many", "msf_check_hypotheses",
+               "msf_find_models", "msf_find_models_device",
                "msf_render_match_image", "msf_weights_info", "msf_convert_weights",
                "msf_frame_cache_stats", "msf_multi_create", "msf_multi_destroy", "msf_multi_device_count",
                "msf_multi_handle", "msf_multi_set_threshold", "msf_multi_last_error", "msf_multi_shard_range",
@@ -52,6 +53,18 @@ class Config(C.Structure):
 
 class Image(C.Structure):
     _fields_ = [("data", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("stride", C.c_int64)]
+
+
+class RansacResult(C.Structure):
+    """msf_ransac_result: host pointers for msf_find_models, device pointers inside a RansacBatch"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("m21", C.c_void_p), ("m12", C.c_void_p),
+                ("fn", C.c_void_p), ("null_vec", C.c_void_p), ("scores", C.c_void_p), ("best", C.c_void_p),
+                ("best_inliers", C.c_void_p), ("T1", C.c_void_p), ("T2", C.c_void_p)]
+
+
+class RansacBatch(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("sets", C.c_void_p),
+                ("homography", RansacResult), ("fundamental", RansacResult)]
 
 
 MATCH_DTYPE = np.dtype([("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4")])
@@ -96,6 +109,8 @@ def load():
     L.msf_store_frame.argtypes = [vp, i32, C.POINTER(Image)]
     L.msf_match_one_to_many.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32]
     L.msf_check_hypotheses.argtypes = [vp, i32, i32, vp, vp, i32, vp, f32, vp, C.POINTER(i32), vp]
+    L.msf_find_models.argtypes = [vp, i32, vp, i32, vp, f32, C.POINTER(RansacResult), C.POINTER(RansacResult)]
+    L.msf_find_models_device.argtypes = [vp, i32, vp, i32, vp, i32, C.c_uint64, f32, C.POINTER(RansacBatch), vp]
     L.msf_render_match_image.argtypes = [vp, C.POINTER(Image), C.POINTER(Image), vp, i32, vp, vp, vp, i64]
     L.msf_weights_info.argtypes = [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(i64)]
     L.msf_convert_weights.argtypes = [C.c_char_p, C.c_char_p]

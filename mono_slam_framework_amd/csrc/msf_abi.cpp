@@ -26,6 +26,12 @@ hipError_t render_match_image(const uint8_t* d_f1, const uint8_t* d_f2, int w, i
 hipError_t check_hypotheses(int model, int n_hyp, const float* d_m21, const float* d_m12, int n,
                             const msf_match* d_matches, float sigma, float* d_scores, uint8_t* d_inliers,
                             hipStream_t st);
+hipError_t find_models(int n_lists, const msf_match* d_matches, int cap, const int32_t* d_n_out, int n_single, int n_hyp,
+                       const int32_t* d_sets, float sigma, float4* d_pn, float* d_T, float* const* d_m21,
+                       float* const* d_aux, float* const* d_null, float* const* d_scores, int32_t* const* d_best,
+                       uint8_t* const* d_inliers, hipStream_t st);
+hipError_t ransac_sets(int n_lists, int n_hyp, const int32_t* d_n_out, int cap, uint64_t seed, int32_t* d_sets,
+                       hipStream_t st);
 }
 
 namespace {
@@ -61,6 +67,9 @@ struct msf_handle {
   uint8_t* d_hyp_inl = nullptr;  // [hyp_cap * hyp_match_cap]
   msf_match* d_hyp_m = nullptr;  // [hyp_match_cap]
   int hyp_cap = 0, hyp_match_cap = 0;
+  // msf_find_models / msf_find_models_device workspace (normalised points, sets, matrices, scores, ...), grown on demand
+  uint8_t* d_fm = nullptr;
+  size_t fm_bytes = 0;
   // msf_render_match_image workspace: the RGB image (allocated once) and the match list + flags (grown on demand)
   uint8_t* d_render = nullptr;      // [H][2 * W][3]
   msf_match* d_render_m = nullptr;  // [render_cap] matches, then 2 * render_cap flag bytes
@@ -401,6 +410,7 @@ void msf_destroy(msf_handle* h) {
   hipFree(h->d_hyp);
   hipFree(h->d_hyp_inl);
   hipFree(h->d_hyp_m);
+  hipFree(h->d_fm);
   hipFree(h->d_render);
   hipFree(h->d_render_m);
   hipFree(h->d_fc_slots);
@@ -761,6 +771,163 @@ int msf_check_hypotheses(msf_handle* h, int32_t model, int32_t n_hyp, const floa
     return MSF_OK;
   } catch (...) {
     return host_exception(h, "msf_check_hypotheses");
+  }
+}
+
+namespace {
+
+// The device arrays of one find-models call: the caller's where it gave one, else a piece of the handle's workspace.
+struct FindModelsPlan {
+  float4* pn = nullptr;
+  float* T = nullptr;
+  int32_t* sets = nullptr;
+  msf_match* matches = nullptr;   // single-list call only
+  float* m21[2] = {}, *aux[2] = {}, *null_vec[2] = {}, *scores[2] = {};
+  int32_t* best[2] = {};
+  uint8_t* inliers[2] = {};
+};
+
+// user: the device pointers the caller supplied.  host_call: the host entry point -- `user` is empty, and the match list
+// and every output get a piece of the workspace.  Returns MSF_OK or an error.
+int plan_find_models(msf_handle* h, int n_lists, int cap, int n_hyp, bool host_call, const msf_ransac_batch* user,
+                     FindModelsPlan* p) {
+  size_t off = 0;
+  auto take = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
+  const size_t L = (size_t)n_lists, LH = L * (size_t)n_hyp;
+  const msf_ransac_result* res[2] = {&user->homography, &user->fundamental};
+  const size_t o_pn = take(L * cap * sizeof(float4)), o_T = take(L * 18 * sizeof(float));
+  const size_t o_sets = user->sets ? 0 : take(LH * 8 * sizeof(int32_t));
+  const size_t o_matches = host_call ? take((size_t)cap * sizeof(msf_match)) : 0;
+  size_t o_m21[2], o_aux[2], o_null[2], o_scores[2], o_best[2], o_inl[2];
+  for (int m = 0; m < 2; m++) {
+    float* user_aux = m == 0 ? res[m]->m12 : res[m]->fn;
+    o_m21[m] = res[m]->m21 ? 0 : take(LH * 9 * sizeof(float));
+    o_aux[m] = user_aux ? 0 : take(LH * 9 * sizeof(float));
+    o_null[m] = host_call ? take(LH * 9 * sizeof(float)) : 0;
+    o_scores[m] = res[m]->scores ? 0 : take((LH ? LH : 1) * sizeof(float));
+    o_best[m] = host_call ? take(sizeof(int32_t)) : 0;
+    o_inl[m] = host_call ? take((size_t)cap) : 0;
+  }
+  if (off > h->fm_bytes) {
+    hipFree(h->d_fm);   // waits for the device: no earlier call still uses the old workspace
+    h->d_fm = nullptr;
+    h->fm_bytes = 0;
+    const size_t want = off > ((size_t)1 << 20) ? off : ((size_t)1 << 20);
+    hipError_t e = hipMalloc(&h->d_fm, want);
+    if (e != hipSuccess) return hip_fail(h, "hipMalloc(find-models workspace)", e);
+    h->fm_bytes = want;
+  }
+  uint8_t* base = h->d_fm;
+  p->pn = reinterpret_cast<float4*>(base + o_pn);
+  p->T = reinterpret_cast<float*>(base + o_T);
+  p->sets = user->sets ? user->sets : reinterpret_cast<int32_t*>(base + o_sets);
+  p->matches = host_call ? reinterpret_cast<msf_match*>(base + o_matches) : nullptr;
+  for (int m = 0; m < 2; m++) {
+    float* user_aux = m == 0 ? res[m]->m12 : res[m]->fn;
+    p->m21[m] = res[m]->m21 ? res[m]->m21 : reinterpret_cast<float*>(base + o_m21[m]);
+    p->aux[m] = user_aux ? user_aux : reinterpret_cast<float*>(base + o_aux[m]);
+    p->null_vec[m] = host_call ? reinterpret_cast<float*>(base + o_null[m]) : res[m]->null_vec;
+    p->scores[m] = res[m]->scores ? res[m]->scores : reinterpret_cast<float*>(base + o_scores[m]);
+    p->best[m] = host_call ? reinterpret_cast<int32_t*>(base + o_best[m]) : res[m]->best;
+    p->inliers[m] = host_call ? base + o_inl[m] : res[m]->best_inliers;
+  }
+  return MSF_OK;
+}
+
+bool ransac_result_ok(const msf_ransac_result* r) {
+  return r && r->struct_size == sizeof(msf_ransac_result) && r->best;
+}
+
+}  // namespace
+
+int msf_find_models(msf_handle* h, int32_t n_matches, const msf_match* matches, int32_t n_hyp, const int32_t* sets,
+                    float sigma, msf_ransac_result* homography, msf_ransac_result* fundamental) {
+  try {
+    if (!h) return MSF_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!ransac_result_ok(homography) || !ransac_result_ok(fundamental) || n_hyp < 0 || n_hyp > (1 << 20) ||
+        n_matches < 0 || n_matches > 8192 || (n_matches > 0 && !matches) ||
+        (n_hyp > 0 && (n_matches < 8 || !sets || !homography->scores || !fundamental->scores)))
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_find_models: bad argument (8 to 8192 matches, sets, best and scores "
+                                          "required, struct_size = sizeof(msf_ransac_result))");
+    for (long long i = 0; i < 8ll * n_hyp; i++)
+      if (sets[i] < 0 || sets[i] >= n_matches)
+        return fail(h, MSF_ERR_INVALID_ARG, "msf_find_models: a set holds an index outside [0, n_matches)");
+    msf_ransac_result* res[2] = {homography, fundamental};
+    for (int m = 0; m < 2; m++) {
+      *res[m]->best = -1;
+      if (res[m]->best_inliers)
+        for (int i = 0; i < n_matches; i++) res[m]->best_inliers[i] = 0;
+    }
+    if (n_hyp == 0) return MSF_OK;
+    hipError_t e = hipSetDevice(h->cfg.device);
+    if (e != hipSuccess) return hip_fail(h, "hipSetDevice", e);
+    // device side: every array is a piece of the workspace
+    msf_ransac_batch dev{};
+    FindModelsPlan p;
+    if (int rc = plan_find_models(h, 1, n_matches, n_hyp, true, &dev, &p)) return rc;
+    hipStream_t st = h->stream;
+    // From here on asynchronous copies from / to the CALLER's buffers are in flight: however the call leaves, the
+    // stream is drained first.
+    struct Drain { hipStream_t s; bool armed = true; ~Drain() { if (armed) hipStreamSynchronize(s); } } drain{st};
+    if ((e = hipMemcpyAsync(p.matches, matches, (size_t)n_matches * sizeof(msf_match), hipMemcpyHostToDevice, st)) != hipSuccess) return hip_fail(h, "hipMemcpyAsync", e);
+    if ((e = hipMemcpyAsync(p.sets, sets, (size_t)n_hyp * 8 * sizeof(int32_t), hipMemcpyHostToDevice, st)) != hipSuccess) return hip_fail(h, "hipMemcpyAsync", e);
+    if ((e = msf::find_models(1, p.matches, n_matches, nullptr, n_matches, n_hyp, p.sets, sigma, p.pn, p.T, p.m21, p.aux,
+                              p.null_vec, p.scores, p.best, p.inliers, st)) != hipSuccess)
+      return hip_fail(h, "find_models", e);
+    const size_t mat_bytes = (size_t)n_hyp * 9 * sizeof(float);
+    auto fetch = [&](void* dst, const void* src, size_t bytes) {
+      return !dst || !bytes ? hipSuccess : hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
+    };
+    for (int m = 0; m < 2; m++) {
+      if ((e = fetch(res[m]->m21, p.m21[m], mat_bytes)) != hipSuccess) return hip_fail(h, "hipMemcpyAsync", e);
+      if ((e = fetch(m == 0 ? res[m]->m12 : res[m]->fn, p.aux[m], mat_bytes)) != hipSuccess) return hip_fail(h, "hipMemcpyAsync", e);
+      if ((e = fetch(res[m]->null_vec, p.null_vec[m], mat_bytes)) != hipSuccess) return hip_fail(h, "hipMemcpyAsync", e);
+      if ((e = fetch(res[m]->scores, p.scores[m], (size_t)n_hyp * sizeof(float))) != hipSuccess) return hip_fail(h, "hipMemcpyAsync", e);
+      if ((e = fetch(res[m]->best, p.best[m], sizeof(int32_t))) != hipSuccess) return hip_fail(h, "hipMemcpyAsync", e);
+      if ((e = fetch(res[m]->best_inliers, p.inliers[m], (size_t)n_matches)) != hipSuccess) return hip_fail(h, "hipMemcpyAsync", e);
+      if ((e = fetch(res[m]->T1, p.T, 9 * sizeof(float))) != hipSuccess) return hip_fail(h, "hipMemcpyAsync", e);
+      if ((e = fetch(res[m]->T2, p.T + 9, 9 * sizeof(float))) != hipSuccess) return hip_fail(h, "hipMemcpyAsync", e);
+    }
+    drain.armed = false;
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(h, "hipStreamSynchronize", e);
+    return MSF_OK;
+  } catch (...) {
+    return host_exception(h, "msf_find_models");
+  }
+}
+
+int msf_find_models_device(msf_handle* h, int32_t n_lists, const msf_match* d_matches, int32_t cap_per_pair,
+                           const int32_t* d_n_out, int32_t n_hyp, uint64_t seed, float sigma, msf_ransac_batch* out,
+                           void* stream) {
+  try {
+    if (!h) return MSF_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!out || out->struct_size != sizeof(msf_ransac_batch) || !ransac_result_ok(&out->homography) ||
+        !ransac_result_ok(&out->fundamental) || n_lists < 0 || n_lists > 65535 || n_hyp < 0 || n_hyp > (1 << 20) ||
+        cap_per_pair < 1 || (n_lists > 0 && (!d_matches || !d_n_out)))
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_find_models_device: bad argument (at most 65535 lists, best required, "
+                                          "struct_size = sizeof(msf_ransac_batch))");
+    if (n_lists == 0) return MSF_OK;
+    hipError_t e = hipSetDevice(h->cfg.device);
+    if (e != hipSuccess) return hip_fail(h, "hipSetDevice", e);
+    FindModelsPlan p;
+    if (int rc = plan_find_models(h, n_lists, cap_per_pair, n_hyp, false, out, &p)) return rc;
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    if ((e = msf::ransac_sets(n_lists, n_hyp, d_n_out, cap_per_pair, seed, p.sets, st)) != hipSuccess)
+      return hip_fail(h, "ransac_sets", e);
+    if ((e = msf::find_models(n_lists, d_matches, cap_per_pair, d_n_out, 0, n_hyp, p.sets, sigma, p.pn, p.T, p.m21, p.aux,
+                              p.null_vec, p.scores, p.best, p.inliers, st)) != hipSuccess)
+      return hip_fail(h, "find_models", e);
+    const msf_ransac_result* res[2] = {&out->homography, &out->fundamental};
+    for (int m = 0; m < 2; m++) {   // T lives as [n_lists][2][9] in the workspace; the caller's T1 / T2 are [n_lists][9] each
+      if (res[m]->T1 && (e = hipMemcpy2DAsync(res[m]->T1, 36, p.T, 72, 36, n_lists, hipMemcpyDeviceToDevice, st)) != hipSuccess) return hip_fail(h, "hipMemcpy2DAsync", e);
+      if (res[m]->T2 && (e = hipMemcpy2DAsync(res[m]->T2, 36, p.T + 9, 72, 36, n_lists, hipMemcpyDeviceToDevice, st)) != hipSuccess) return hip_fail(h, "hipMemcpy2DAsync", e);
+    }
+    if (!stream && (e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(h, "hipStreamSynchronize", e);
+    return MSF_OK;
+  } catch (...) {
+    return host_exception(h, "msf_find_models_device");
   }
 }
 

@@ -166,6 +166,63 @@ class _Matcher:
                                                  float(sigma), scores.ctypes.data, C.byref(best), inl.ctypes.data))
         return best.value, scores, inl[:len(m)].astype(bool)
 
+    def find_models(self, matches, sets, sigma=1.0):
+        """Initializer::FindHomography + FindFundamental (Initializer.cc:152-245) with the hypotheses made on the device:
+        matches int32 [n, 4], sets int32 [n_hyp, 8] (mvSets).  -> {"H": ..., "F": ...}, each a dict with m21 [n_hyp, 3, 3],
+        null_vec [n_hyp, 3, 3], scores [n_hyp], best (index or -1), best_inliers bool [n], T1, T2 [3, 3], and m12 (H) or
+        fn (F) [n_hyp, 3, 3]; scores / best / best_inliers are those of check_hypotheses on m21 / m12."""
+        m = np.ascontiguousarray(matches, np.int32).reshape(-1, 4)
+        sets = np.ascontiguousarray(sets, np.int32).reshape(-1, 8)
+        n, n_hyp = len(m), len(sets)
+        out, res = {}, []
+        for name in ("H", "F"):
+            d = dict(m21=np.zeros((n_hyp, 3, 3), np.float32), null_vec=np.zeros((n_hyp, 3, 3), np.float32),
+                     scores=np.zeros(n_hyp, np.float32), best=np.full(1, -1, np.int32),
+                     best_inliers=np.zeros(max(n, 1), np.uint8), T1=np.zeros((3, 3), np.float32),
+                     T2=np.zeros((3, 3), np.float32))
+            d["m12" if name == "H" else "fn"] = np.zeros((n_hyp, 3, 3), np.float32)
+            r = _lib.RansacResult(struct_size=C.sizeof(_lib.RansacResult))
+            for k, v in d.items():
+                setattr(r, k, v.ctypes.data)
+            out[name] = d
+            res.append(r)
+        self._check(self._L.msf_find_models(self._h, n, m.ctypes.data, n_hyp, sets.ctypes.data, float(sigma),
+                                            C.byref(res[0]), C.byref(res[1])))
+        for d in out.values():
+            d["best"] = int(d["best"][0])
+            d["best_inliers"] = d["best_inliers"][:n].astype(bool)
+        return out
+
+    def find_models_device(self, d_matches, d_n_out, n_hyp=200, seed=0, sigma=1.0, stream=None):
+        """The same for the lists of a batch in device memory: d_matches int32 CUDA tensor [n_lists, cap, 4] and d_n_out
+        int32 [n_lists], as match_batch_device leaves them; the sets are drawn on the device from `seed`.
+        -> {"sets": int32 [n_lists, n_hyp, 8], "H": ..., "F": ...} of CUDA tensors with a leading n_lists dimension
+        (keys as find_models; best int32 [n_lists], best_inliers uint8 [n_lists, cap]).  Lists shorter than 8 or longer
+        than 8192 get best = -1.  Asynchronous on `stream` (None = handle stream + sync)."""
+        import torch
+        assert d_matches.is_cuda and d_n_out.is_cuda and d_matches.is_contiguous() and d_n_out.is_contiguous()
+        assert d_matches.dtype == torch.int32 and d_n_out.dtype == torch.int32
+        L, cap = d_matches.shape[0], d_matches.shape[1]
+        dev = d_matches.device
+
+        def z(shape, dtype=torch.float32):
+            return torch.zeros(shape, dtype=dtype, device=dev)
+
+        out = {"sets": z((L, n_hyp, 8), torch.int32)}
+        batch = _lib.RansacBatch(struct_size=C.sizeof(_lib.RansacBatch), sets=out["sets"].data_ptr())
+        for name, r in (("H", batch.homography), ("F", batch.fundamental)):
+            d = dict(m21=z((L, n_hyp, 3, 3)), null_vec=z((L, n_hyp, 3, 3)), scores=z((L, n_hyp)),
+                     best=torch.full((L,), -1, dtype=torch.int32, device=dev), best_inliers=z((L, cap), torch.uint8),
+                     T1=z((L, 3, 3)), T2=z((L, 3, 3)))
+            d["m12" if name == "H" else "fn"] = z((L, n_hyp, 3, 3))
+            r.struct_size = C.sizeof(_lib.RansacResult)
+            for k, v in d.items():
+                setattr(r, k, v.data_ptr())
+            out[name] = d
+        self._check(self._L.msf_find_models_device(self._h, L, d_matches.data_ptr(), cap, d_n_out.data_ptr(), n_hyp,
+                                                   int(seed), float(sigma), C.byref(batch), stream))
+        return out
+
     def render_match_image(self, frame1, frame2, matches, has_mp1=None, has_mp2=None):
         """Tracking::CreateCurrentMatchImage (Tracking.cc:899-940) -> uint8 [H, 2W, 3]."""
         a, b = self._image(frame1), self._image(frame2)
