@@ -633,6 +633,9 @@ __device__ __forceinline__ int stream_score(const uint8_t* ring, uint32_t r0, ui
 // on the reading side; thresholds may differ from run to run in principle, the candidate lists they lead to contain
 // every corner retainBest(2N) can keep either way (k_fast_check).
 constexpr uint32_t kSpinMax = 1u << 19;
+// A vector offset no level the walker makes reaches (host-checked: such a level is below 1 GB): the buffer range check
+// drops a store at it, whatever row offset comes on top.  dxoff | kRzNoStore stays in [1 GB, 2 GB).
+constexpr uint32_t kRzNoStore = 0x40000000u;
 
 
 __device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) {
@@ -786,7 +789,7 @@ __device__ __forceinline__ void walk_strip(StreamSmem& sm, const OrbGeometry& g,
   // ---- resize state: this lane's group of 4 output columns of level l + 1
   uint32_t rsel[4] = {0, 0, 0, 0}, rwxp[4] = {0, 0, 0, 0}, roff0 = 0, roff3 = 0, em0 = 0, em1 = 0, em2 = 0, em3 = 0;
   __amdgpu_buffer_rsrc_t dst_rs = img_rs;         // level l + 1 of this frame (set below)
-  uint32_t dxoff = 0;                             // the lane's byte offset inside an output row
+  uint32_t dxoff = 0;                             // the lane's byte offset inside an output row, or kRzNoStore
   bool rz_lane = false;
   uint32_t dpitch = 0;
   if (RESIZE) {
@@ -808,7 +811,7 @@ __device__ __forceinline__ void walk_strip(StreamSmem& sm, const OrbGeometry& g,
     roff3 = rz_lane ? qov.w - (uint32_t)xs : 0u;
     dpitch = uniform_u32((uint32_t)Ld.pitch);
     dst_rs = uniform_rsrc(pyr + (long long)slot * g.pyr_bytes + Ld.pix_off, (uint32_t)Ld.h * (uint32_t)Ld.pitch);
-    dxoff = 4u * (uint32_t)gq;
+    dxoff = rz_lane ? 4u * (uint32_t)gq : kRzNoStore;
     // emit entries of the source rows R0 - 4 + j, j = 64 k + lane in em<k>: output row | w1 << 16 | 1 << 31
     // if an output row has source rows (y, y + 1) as its taps and y is owned by this strip
     const int ra = R0 - 4 + lane, rb = ra + 64;
@@ -850,16 +853,21 @@ __device__ __forceinline__ void walk_strip(StreamSmem& sm, const OrbGeometry& g,
     const int jj_ = (j_);                                                                                              \
     /* one select + one v_readlane (a ternary of two readlanes compiles to branches) */                                 \
     const uint32_t em_ = (uint32_t)__builtin_amdgcn_readlane((int)((jj_ >> 6) == em_k ? em_a : em_b), jj_ & 63);        \
-    if ((int)em_ < 0) {                                                                                                \
-      const uint32_t wy1_ = (em_ >> 16) & 0x1FFu, wy0_ = 256u - wy1_, rnd_ = 32768u;                                   \
-      const uint32_t v0_ = mad_u24_s(hu_[0], wy0_, mad_u24_s(hl_[0], wy1_, rnd_));                                     \
-      const uint32_t v1_ = mad_u24_s(hu_[1], wy0_, mad_u24_s(hl_[1], wy1_, rnd_));                                     \
-      const uint32_t v2_ = mad_u24_s(hu_[2], wy0_, mad_u24_s(hl_[2], wy1_, rnd_));                                     \
-      const uint32_t v3_ = mad_u24_s(hu_[3], wy0_, mad_u24_s(hl_[3], wy1_, rnd_));                                     \
-      const uint32_t pk_ = __builtin_amdgcn_perm(v1_, v0_, 0x0c0c0602u) | __builtin_amdgcn_perm(v3_, v2_, 0x06020c0cu); \
-      /* aux 16 = sc1: write-through, so that the level is in memory when this strip counts itself done (k_walk) */     \
-      if (rz_lane) __builtin_amdgcn_raw_buffer_store_b32(pk_, dst_rs, dxoff, (em_ & 0xFFFFu) * dpitch, 16);             \
-    }                                                                                                                  \
+    const uint32_t wy1_ = (em_ >> 16) & 0x1FFu, wy0_ = 256u - wy1_, rnd_ = 32768u;                                     \
+    const uint32_t v0_ = mad_u24_s(hu_[0], wy0_, mad_u24_s(hl_[0], wy1_, rnd_));                                       \
+    const uint32_t v1_ = mad_u24_s(hu_[1], wy0_, mad_u24_s(hl_[1], wy1_, rnd_));                                       \
+    const uint32_t v2_ = mad_u24_s(hu_[2], wy0_, mad_u24_s(hl_[2], wy1_, rnd_));                                       \
+    const uint32_t v3_ = mad_u24_s(hu_[3], wy0_, mad_u24_s(hl_[3], wy1_, rnd_));                                       \
+    const uint32_t pk_ = __builtin_amdgcn_perm(v1_, v0_, 0x0c0c0602u) | __builtin_amdgcn_perm(v3_, v2_, 0x06020c0cu);   \
+    /* Always issued, no branch around it: every row group then holds the same number of vector-memory operations */   \
+    /* on every path, and the wait for the next group's pixel rows can be a counted one that leaves these stores */    \
+    /* in flight (the counter takes loads and stores together, in order).  A source row without an output row */       \
+    /* (bit 31 of its entry clear) and a lane without an output group store at kRzNoStore, the former at row 0: */      \
+    /* dropped by the range check.  aux 16 = sc1: write-through, so that the level is in memory when this strip */      \
+    /* counts itself done (k_walk). */                                                                                 \
+    const bool has_ = (int)em_ < 0;                                                                                    \
+    __builtin_amdgcn_raw_buffer_store_b32(pk_, dst_rs, dxoff | (has_ ? 0u : kRzNoStore),                                \
+                                          (has_ ? em_ & 0xFFFFu : 0u) * dpitch, 16);                                   \
   } while (0)
 
   auto flush_out = [&]() {
@@ -900,7 +908,7 @@ __device__ __forceinline__ void walk_strip(StreamSmem& sm, const OrbGeometry& g,
   };
 
   // scores everything recorded so far (rel rows <= s), then NMS of rel rows [nms_lo, s - 1]
-  auto flush = [&](int s) {
+  auto flush = [&](int s) __attribute__((always_inline)) {
     // the hit list was rebuilt from one row's scores at the end of the last flush: if that row held more corners than
     // the list, this NMS is the dense one
     bool overflow = nH > (uint32_t)kSHCap;
@@ -1111,7 +1119,7 @@ __device__ __forceinline__ void walk_strip(StreamSmem& sm, const OrbGeometry& g,
   STREAM_PRE_DOWN(w0_, w3_, pb1, pn1);
   STREAM_PRE_DOWN(w1_, w4_, pb2, pn2);
   STREAM_PRE_DOWN(w2_, w5_, pb3, pn3);
-  auto group = [&](auto ph_, const int s) {
+  auto group = [&](auto ph_, const int s) __attribute__((always_inline)) {
     constexpr int P_ = decltype(ph_)::value * 4;
     if (RESIZE && ((s + 5) >> 6) != em_k) {          // uniform, once per 64 rows: the window of the emit table moves on
       em_k++;
@@ -1160,20 +1168,33 @@ __device__ __forceinline__ void walk_strip(StreamSmem& sm, const OrbGeometry& g,
     STREAM_APPEND(s + 2, cb2, cd2);
     STREAM_APPEND(s + 3, cb3, cd3);
   };
-  for (int s = 0; s <= r_last; s += 4) {
-    switch ((s >> 2) & 3) {
-      case 0: group(std::integral_constant<int, 0>{}, s); break;
-      case 1: group(std::integral_constant<int, 1>{}, s); break;
-      case 2: group(std::integral_constant<int, 2>{}, s); break;
-      default: group(std::integral_constant<int, 3>{}, s); break;
-    }
+  // what follows a group: the flush if one is due; true after the strip's last group
+  auto after = [&](const int s) __attribute__((always_inline)) {
     const int sl = min(s + 3, r_last);
     // flushes happen between groups of four steps: at most kSGFlush + 4 x 64 records wait (kSGCap), at most 8 rows
     if (do_fast && (nG > kSGFlush || sl - last_flush >= kFlushRows || sl == r_last)) {
       MSF_WAVE_SYNC();
       flush(sl);
     }
-  }
+    return s + 4 > r_last;
+  };
+  // The four copies of the group body follow one another in ONE loop body (16 rows per trip).  As the four cases of a
+  // switch they met in a common block before the back edge, where the compiler moved everything a group hands to the
+  // next -- the queued rows, the "below" bits, the resize sums, the emit blocks: 16 v_mov per group -- into the
+  // registers the loop header expects, and waited there, at the end of the group that had requested them, for the queued
+  // rows.  In sequence each copy reads what the one before it left where it left it, and the wait for a queued row
+  // stands at its first use: a counted one (vmcnt(6), vmcnt(4)) behind the group's four stores (RZ_EMIT).
+  if (r_last >= 0)
+    for (int s = 0;; s += 16) {
+      group(std::integral_constant<int, 0>{}, s);
+      if (after(s)) break;
+      group(std::integral_constant<int, 1>{}, s + 4);
+      if (after(s + 4)) break;
+      group(std::integral_constant<int, 2>{}, s + 8);
+      if (after(s + 8)) break;
+      group(std::integral_constant<int, 3>{}, s + 12);
+      if (after(s + 12)) break;
+    }
 #undef STREAM_PRE
 #undef STREAM_PRE_DOWN
 #undef STREAM_APPEND
@@ -2548,6 +2569,7 @@ std::string OrbPipeline::init(int width, int height, int max_slots, bool blur_ha
     // upper tap of at most one output row, the shared-pair column form holds, and every strip's groups fit its window
     const OrbLevelInfo& Ls = g.lv[l - 1];
     bool fused = shared && Ls.wk_rows <= kWkMaxRows && Ls.h < 65536;
+    if ((long long)L.pitch * L.h >= (long long)kRzNoStore) fused = false;   // the offset of a dropped store must lie past the level
     uint32_t* yemit = htab.data() + L.tab_yemit;
     uint32_t* xstrip = htab.data() + L.tab_xstrip;
     for (int y = 0; y < L.h; y++) {
