@@ -1,4 +1,4 @@
-"""ctypes view of include/msf_abi.h.  Loading fails loudly when libmsf.so is missing: there is no CPU fallback."""
+"""ctypes view of include/msf_abi.h and include/msf_initializer.h.  Loading fails loudly when libmsf.so is missing: there is no CPU fallback."""
 import ctypes as C
 import os
 
@@ -44,6 +44,9 @@ ABI_SYMBOLS = ["msf_abi_version", "msf_default_config", "msf_create", "msf_destr
                "msf_gather_unique_id", "msf_gather_create", "msf_gather_destroy", "msf_gather_last_error",
                "msf_gather_plan", "msf_gather_matches_device"]
 
+# every symbol include/msf_initializer.h declares (a header and a version of its own: MSF_ABI_VERSION stays what it is)
+INITIALIZER_SYMBOLS = ["msf_initializer_version", "msf_reconstruct", "msf_reconstruct_device"]
+
 
 class Config(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_int32), ("device", C.c_int32), ("threshold", C.c_float),
@@ -65,6 +68,20 @@ class RansacResult(C.Structure):
 class RansacBatch(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("sets", C.c_void_p),
                 ("homography", RansacResult), ("fundamental", RansacResult)]
+
+
+class MotionParams(C.Structure):
+    """msf_motion_params: Initializer(K, sigma) + Initialize(..., minTriangulated, minParallax)"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("K", C.c_float * 9), ("sigma", C.c_float),
+                ("min_triangulated", C.c_int32), ("min_parallax", C.c_float)]
+
+
+class MotionResult(C.Structure):
+    """msf_motion_result: host pointers for msf_reconstruct, device pointers [n_lists] for msf_reconstruct_device"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("ok", C.c_void_p), ("model", C.c_void_p),
+                ("R21", C.c_void_p), ("t21", C.c_void_p), ("points", C.c_void_p), ("triangulated", C.c_void_p),
+                ("n_cand", C.c_void_p), ("cand_R", C.c_void_p), ("cand_t", C.c_void_p), ("cand_good", C.c_void_p),
+                ("cand_parallax", C.c_void_p), ("winner", C.c_void_p)]
 
 
 MATCH_DTYPE = np.dtype([("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4")])
@@ -111,6 +128,10 @@ def load():
     L.msf_check_hypotheses.argtypes = [vp, i32, i32, vp, vp, i32, vp, f32, vp, C.POINTER(i32), vp]
     L.msf_find_models.argtypes = [vp, i32, vp, i32, vp, f32, C.POINTER(RansacResult), C.POINTER(RansacResult)]
     L.msf_find_models_device.argtypes = [vp, i32, vp, i32, vp, i32, C.c_uint64, f32, C.POINTER(RansacBatch), vp]
+    L.msf_initializer_version.restype = C.c_int
+    L.msf_reconstruct.argtypes = [vp, i32, vp, i32, vp, vp, C.POINTER(MotionParams), C.POINTER(MotionResult)]
+    L.msf_reconstruct_device.argtypes = [vp, i32, vp, i32, vp, i32, C.POINTER(RansacBatch), C.POINTER(MotionParams),
+                                         C.POINTER(MotionResult), vp]
     L.msf_render_match_image.argtypes = [vp, C.POINTER(Image), C.POINTER(Image), vp, i32, vp, vp, vp, i64]
     L.msf_weights_info.argtypes = [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(i64)]
     L.msf_convert_weights.argtypes = [C.c_char_p, C.c_char_p]

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -11,7 +12,10 @@
 #include <vector>
 
 #include "loftr_pipeline.h"
+#include "msf_initializer.h"
 #include "orb_pipeline.h"
+#include "ransac_solve.h"
+#include "reconstruct_pipeline.h"
 #include "weights_io.h"
 
 namespace msf {
@@ -94,6 +98,8 @@ struct msf_handle {
   int hyp_cap = 0, hyp_match_cap = 0;
   // msf_find_models / msf_find_models_device workspace (normalised points, sets, matrices, scores, ...), grown on demand
   DevBuf<uint8_t> d_fm;
+  // msf_reconstruct / msf_reconstruct_device workspace (candidates, counts, the host call's list and results), grown on demand
+  DevBuf<uint8_t> d_rc;
   // msf_render_match_image workspace: the RGB image (allocated once) and the match list + flags (grown on demand)
   DevBuf<uint8_t> d_render;      // [H][2 * W][3]
   DevBuf<msf_match> d_render_m;  // [cap] matches, then 2 * cap flag bytes; cap = bytes / kRenderRecord
@@ -906,6 +912,184 @@ int msf_find_models_device(msf_handle* h, int32_t n_lists, const msf_match* d_ma
       if (res[m]->T1) HIP_TRY(h, "hipMemcpy2DAsync", hipMemcpy2DAsync(res[m]->T1, 36, p.T, 72, 36, n_lists, hipMemcpyDeviceToDevice, st));
       if (res[m]->T2) HIP_TRY(h, "hipMemcpy2DAsync", hipMemcpy2DAsync(res[m]->T2, 36, p.T + 9, 72, 36, n_lists, hipMemcpyDeviceToDevice, st));
     }
+    return cs.finish();
+  });
+}
+
+// ---- msf_initializer.h: the tail of Initializer::Initialize ----
+namespace {
+
+// The device arrays of one reconstruct call: the caller's where it gave one, else a piece of the handle's workspace.
+struct ReconstructPlan {
+  msf::MotionOut out{};
+  msf_match* matches = nullptr;   // host call only: the list, its inlier flags and its matrix
+  uint8_t* inliers = nullptr;
+  float* m21 = nullptr;
+};
+
+// user: the device pointers the caller supplied (the host entry point passes an empty struct and gets a piece of the
+// workspace for every output, the list included).  points / triangulated are only produced where somebody reads them.
+int plan_reconstruct(msf_handle* h, int n_lists, int cap, bool host_call, const msf_motion_result* user,
+                     const msf_motion_result* wanted, ReconstructPlan* p) {
+  size_t off = 0;
+  auto take = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
+  const size_t L = (size_t)n_lists;
+  auto piece = [&](const void* given, size_t bytes) { return given ? (size_t)0 : take(bytes); };
+  const size_t o_ok = piece(user->ok, L * 4), o_model = piece(user->model, L * 4), o_ninl = take(L * 4);
+  const size_t o_ncand = piece(user->n_cand, L * 4), o_cr = piece(user->cand_R, L * 72 * 4);
+  const size_t o_ct = piece(user->cand_t, L * 24 * 4), o_cg = piece(user->cand_good, L * 8 * 4);
+  const size_t o_cp = piece(user->cand_parallax, L * 8 * 4), o_win = piece(user->winner, L * 4);
+  const size_t o_R = piece(user->R21, L * 9 * 4), o_t = piece(user->t21, L * 3 * 4);
+  const bool want_points = host_call && wanted->points, want_tri = host_call && wanted->triangulated;
+  const size_t o_pts = want_points ? take(L * cap * 12) : 0, o_tri = want_tri ? take(L * cap) : 0;
+  const size_t o_matches = host_call ? take((size_t)cap * sizeof(msf_match)) : 0;
+  const size_t o_inl = host_call ? take((size_t)cap) : 0, o_m21 = host_call ? take(9 * 4) : 0;
+  if (off > h->d_rc.bytes) HIP_TRY(h, "hipMalloc(reconstruct workspace)", h->d_rc.reserve(off, (size_t)1 << 16));
+  uint8_t* base = h->d_rc;
+  auto at = [&](auto* given, size_t o) { return given ? given : reinterpret_cast<decltype(given)>(base + o); };
+  p->out.ok = at(user->ok, o_ok);
+  p->out.model = at(user->model, o_model);
+  p->out.n_inliers = reinterpret_cast<int32_t*>(base + o_ninl);
+  p->out.n_cand = at(user->n_cand, o_ncand);
+  p->out.cand_R = at(user->cand_R, o_cr);
+  p->out.cand_t = at(user->cand_t, o_ct);
+  p->out.cand_good = at(user->cand_good, o_cg);
+  p->out.cand_parallax = at(user->cand_parallax, o_cp);
+  p->out.winner = at(user->winner, o_win);
+  p->out.R21 = at(user->R21, o_R);
+  p->out.t21 = at(user->t21, o_t);
+  p->out.points = host_call ? (want_points ? reinterpret_cast<float*>(base + o_pts) : nullptr) : user->points;
+  p->out.triangulated = host_call ? (want_tri ? base + o_tri : nullptr) : user->triangulated;
+  if (host_call) {
+    p->matches = reinterpret_cast<msf_match*>(base + o_matches);
+    p->inliers = base + o_inl;
+    p->m21 = reinterpret_cast<float*>(base + o_m21);
+  }
+  return MSF_OK;
+}
+
+// nullptr when the parameters are usable, else what is wrong with them
+const char* motion_params_fault(const msf_motion_params* prm) {
+  if (!prm) return "params is NULL";
+  if (prm->struct_size != sizeof(msf_motion_params)) return "params->struct_size is not sizeof(msf_motion_params)";
+  bool finite = std::isfinite(prm->sigma) && std::isfinite(prm->min_parallax);
+  for (int k = 0; k < 9; k++) finite = finite && std::isfinite(prm->K[k]);
+  if (!finite) return "K, sigma and min_parallax must be finite";
+  float inv[9];
+  msf::ransac::inv3(prm->K, inv);
+  bool zero = true;
+  for (int k = 0; k < 9; k++) zero = zero && inv[k] == 0.0f;
+  if (zero) return "K is singular";
+  return nullptr;
+}
+
+msf::MotionParams motion_params(const msf_motion_params* prm) {
+  msf::MotionParams d{};
+  for (int k = 0; k < 9; k++) d.K[k] = prm->K[k];
+  d.th2 = 4.0f * (prm->sigma * prm->sigma);   // 4.0f * mSigma2
+  d.min_triangulated = prm->min_triangulated;
+  d.min_parallax = prm->min_parallax;
+  return d;
+}
+
+}  // namespace
+
+int msf_initializer_version(void) { return MSF_INITIALIZER_VERSION; }
+
+int msf_reconstruct(msf_handle* h, int32_t model, const float* m21, int32_t n_matches, const msf_match* matches,
+                    const uint8_t* inliers, const msf_motion_params* params, msf_motion_result* out) {
+  return guarded(h, "msf_reconstruct", [&]() -> int {
+    if (!out || out->struct_size != sizeof(msf_motion_result))
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_reconstruct: out is NULL or out->struct_size is not sizeof(msf_motion_result)");
+    if (!out->ok || !m21 || (n_matches > 0 && (!matches || !inliers)))
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_reconstruct: a required pointer is NULL (m21, matches, inliers, out->ok)");
+    if (n_matches < 0 || n_matches > msf::kMaxReconstructMatches)
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_reconstruct: n_matches outside [0, 8192]");
+    if (model != MSF_MODEL_HOMOGRAPHY && model != MSF_MODEL_FUNDAMENTAL)
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_reconstruct: model is neither MSF_MODEL_HOMOGRAPHY nor MSF_MODEL_FUNDAMENTAL");
+    if (const char* fault = motion_params_fault(params))
+      return fail(h, MSF_ERR_INVALID_ARG, std::string("msf_reconstruct: ") + fault);
+    CallScope cs{h};
+    if (int rc = cs.enter()) return rc;
+    const int cap = n_matches > 0 ? n_matches : 1;
+    const msf_motion_result none{};
+    ReconstructPlan p;
+    if (int rc = plan_reconstruct(h, 1, cap, true, &none, out, &p)) return rc;
+    hipStream_t st = cs.st;
+    Drain drain{st};
+    if (n_matches > 0) {
+      HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.matches, matches, (size_t)n_matches * sizeof(msf_match), hipMemcpyHostToDevice, st));
+      HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.inliers, inliers, (size_t)n_matches, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.m21, m21, 9 * sizeof(float), hipMemcpyHostToDevice, st));
+    msf::MotionLists in{};
+    in.matches = p.matches;
+    in.cap = cap;
+    in.n_single = n_matches;
+    in.n_hyp = 1;
+    in.forced_model = model;
+    in.m21[model] = p.m21;
+    in.inliers[model] = p.inliers;
+    HIP_TRY(h, "reconstruct_motion", msf::reconstruct_motion(1, in, motion_params(params), p.out, st));
+    auto fetch = [&](void* dst, const void* src, size_t bytes) {
+      return !dst || !bytes ? hipSuccess : hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
+    };
+    HIP_TRY(h, "hipMemcpyAsync", fetch(out->ok, p.out.ok, 4));
+    HIP_TRY(h, "hipMemcpyAsync", fetch(out->model, p.out.model, 4));
+    HIP_TRY(h, "hipMemcpyAsync", fetch(out->R21, p.out.R21, 9 * 4));
+    HIP_TRY(h, "hipMemcpyAsync", fetch(out->t21, p.out.t21, 3 * 4));
+    HIP_TRY(h, "hipMemcpyAsync", fetch(out->points, p.out.points, (size_t)n_matches * 12));
+    HIP_TRY(h, "hipMemcpyAsync", fetch(out->triangulated, p.out.triangulated, (size_t)n_matches));
+    HIP_TRY(h, "hipMemcpyAsync", fetch(out->n_cand, p.out.n_cand, 4));
+    HIP_TRY(h, "hipMemcpyAsync", fetch(out->cand_R, p.out.cand_R, 72 * 4));
+    HIP_TRY(h, "hipMemcpyAsync", fetch(out->cand_t, p.out.cand_t, 24 * 4));
+    HIP_TRY(h, "hipMemcpyAsync", fetch(out->cand_good, p.out.cand_good, 8 * 4));
+    HIP_TRY(h, "hipMemcpyAsync", fetch(out->cand_parallax, p.out.cand_parallax, 8 * 4));
+    HIP_TRY(h, "hipMemcpyAsync", fetch(out->winner, p.out.winner, 4));
+    drain.armed = false;
+    return cs.finish();   // the one wait of the call
+  });
+}
+
+int msf_reconstruct_device(msf_handle* h, int32_t n_lists, const msf_match* d_matches, int32_t cap_per_pair,
+                           const int32_t* d_n_out, int32_t n_hyp, const msf_ransac_batch* found,
+                           const msf_motion_params* params, msf_motion_result* out, void* stream) {
+  return guarded(h, "msf_reconstruct_device", [&]() -> int {
+    if (!out || out->struct_size != sizeof(msf_motion_result))
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_reconstruct_device: out is NULL or out->struct_size is not sizeof(msf_motion_result)");
+    if (!found || found->struct_size != sizeof(msf_ransac_batch))
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_reconstruct_device: found is NULL or found->struct_size is not sizeof(msf_ransac_batch)");
+    const msf_ransac_result* res[2] = {&found->homography, &found->fundamental};
+    bool complete = out->ok && (n_lists <= 0 || (d_matches && d_n_out));
+    for (int m = 0; m < 2; m++)
+      complete = complete && res[m]->m21 && res[m]->scores && res[m]->best && res[m]->best_inliers;
+    if (!complete)
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_reconstruct_device: a required pointer is NULL (d_matches, d_n_out, out->ok; "
+                                          "m21, scores, best and best_inliers of both models of found)");
+    if (n_lists < 0 || n_lists > 65535)
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_reconstruct_device: n_lists outside [0, 65535]");
+    if (cap_per_pair < 1 || n_hyp < 1 || n_hyp > (1 << 20))
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_reconstruct_device: cap_per_pair < 1 or n_hyp outside [1, 2^20]");
+    if (const char* fault = motion_params_fault(params))
+      return fail(h, MSF_ERR_INVALID_ARG, std::string("msf_reconstruct_device: ") + fault);
+    if (n_lists == 0) return MSF_OK;
+    CallScope cs{h};
+    if (int rc = cs.enter(stream)) return rc;
+    ReconstructPlan p;
+    if (int rc = plan_reconstruct(h, n_lists, cap_per_pair, false, out, out, &p)) return rc;
+    msf::MotionLists in{};
+    in.matches = d_matches;
+    in.cap = cap_per_pair;
+    in.n_out = d_n_out;
+    in.n_hyp = n_hyp;
+    in.forced_model = -1;
+    for (int m = 0; m < 2; m++) {
+      in.m21[m] = res[m]->m21;
+      in.scores[m] = res[m]->scores;
+      in.best[m] = res[m]->best;
+      in.inliers[m] = res[m]->best_inliers;
+    }
+    HIP_TRY(h, "reconstruct_motion", msf::reconstruct_motion(n_lists, in, motion_params(params), p.out, cs.st));
     return cs.finish();
   });
 }

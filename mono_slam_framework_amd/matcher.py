@@ -223,6 +223,76 @@ class _Matcher:
                                                    int(seed), float(sigma), C.byref(batch), stream))
         return out
 
+    @staticmethod
+    def _motion_params(K, sigma, min_triangulated, min_parallax):
+        prm = _lib.MotionParams(struct_size=C.sizeof(_lib.MotionParams), sigma=float(sigma),
+                                min_triangulated=int(min_triangulated), min_parallax=float(min_parallax))
+        prm.K[:] = [float(v) for v in np.asarray(K, np.float32).reshape(9)]
+        return prm
+
+    def reconstruct(self, model, m21, matches, inliers, K, sigma=1.0, min_triangulated=50, min_parallax=1.0):
+        """Initializer::ReconstructH (model 0) / ReconstructF (model 1) (Initializer.cc:489-934) of one list: m21 [3, 3]
+        the H21 / F21, matches int32 [n, 4], inliers bool [n] (vbMatchesInliers), K [3, 3].  -> dict: ok, model (-1: no
+        list to reconstruct from), R21 [3, 3], t21 [3], points f32 [n, 3] (vP3D), triangulated bool [n], and the
+        diagnostics n_cand, cand_R [8, 3, 3], cand_t [8, 3], cand_good [8], cand_parallax [8], winner."""
+        m = np.ascontiguousarray(matches, np.int32).reshape(-1, 4)
+        n = len(m)
+        inl = np.ascontiguousarray(np.asarray(inliers).reshape(-1), np.uint8)
+        if len(inl) != n:
+            raise ValueError("one inlier flag per match")
+        m21 = np.ascontiguousarray(m21, np.float32).reshape(9)
+        d = dict(ok=np.zeros(1, np.int32), model=np.zeros(1, np.int32), R21=np.zeros((3, 3), np.float32),
+                 t21=np.zeros(3, np.float32), points=np.zeros((max(n, 1), 3), np.float32),
+                 triangulated=np.zeros(max(n, 1), np.uint8), n_cand=np.zeros(1, np.int32),
+                 cand_R=np.zeros((8, 3, 3), np.float32), cand_t=np.zeros((8, 3), np.float32),
+                 cand_good=np.zeros(8, np.int32), cand_parallax=np.zeros(8, np.float32), winner=np.zeros(1, np.int32))
+        res = _lib.MotionResult(struct_size=C.sizeof(_lib.MotionResult))
+        for k, v in d.items():
+            setattr(res, k, v.ctypes.data)
+        prm = self._motion_params(K, sigma, min_triangulated, min_parallax)
+        self._check(self._L.msf_reconstruct(self._h, int(model), m21.ctypes.data, n, m.ctypes.data, inl.ctypes.data,
+                                            C.byref(prm), C.byref(res)))
+        for k in ("ok", "model", "n_cand", "winner"):
+            d[k] = int(d[k][0])
+        d["points"] = d["points"][:n]
+        d["triangulated"] = d["triangulated"][:n].astype(bool)
+        return d
+
+    def reconstruct_device(self, d_matches, d_n_out, found, K, sigma=1.0, min_triangulated=50, min_parallax=1.0,
+                           stream=None):
+        """The tail of Initializer::Initialize for the lists of a batch in device memory: `found` is what
+        find_models_device returned for the same d_matches / d_n_out; H or F is chosen per list by RH.
+        -> dict of CUDA tensors with a leading n_lists dimension (keys as reconstruct; points [n_lists, cap, 3],
+        triangulated uint8 [n_lists, cap]).  Asynchronous on `stream` (None = handle stream + sync)."""
+        import torch
+        assert d_matches.is_cuda and d_n_out.is_cuda and d_matches.is_contiguous() and d_n_out.is_contiguous()
+        assert d_matches.dtype == torch.int32 and d_n_out.dtype == torch.int32
+        L, cap = d_matches.shape[0], d_matches.shape[1]
+        dev = d_matches.device
+        n_hyp = found["H"]["scores"].shape[1]
+        batch = _lib.RansacBatch(struct_size=C.sizeof(_lib.RansacBatch), sets=found["sets"].data_ptr())
+        for name, r in (("H", batch.homography), ("F", batch.fundamental)):
+            r.struct_size = C.sizeof(_lib.RansacResult)
+            for k in ("m21", "scores", "best", "best_inliers"):
+                t = found[name][k]
+                assert t.is_cuda and t.is_contiguous() and t.shape[0] == L
+                setattr(r, k, t.data_ptr())
+
+        def z(shape, dtype=torch.float32):
+            return torch.zeros(shape, dtype=dtype, device=dev)
+
+        i32 = torch.int32
+        d = dict(ok=z((L,), i32), model=z((L,), i32), R21=z((L, 3, 3)), t21=z((L, 3)), points=z((L, cap, 3)),
+                 triangulated=z((L, cap), torch.uint8), n_cand=z((L,), i32), cand_R=z((L, 8, 3, 3)), cand_t=z((L, 8, 3)),
+                 cand_good=z((L, 8), i32), cand_parallax=z((L, 8)), winner=z((L,), i32))
+        res = _lib.MotionResult(struct_size=C.sizeof(_lib.MotionResult))
+        for k, v in d.items():
+            setattr(res, k, v.data_ptr())
+        prm = self._motion_params(K, sigma, min_triangulated, min_parallax)
+        self._check(self._L.msf_reconstruct_device(self._h, L, d_matches.data_ptr(), cap, d_n_out.data_ptr(), n_hyp,
+                                                   C.byref(batch), C.byref(prm), C.byref(res), stream))
+        return d
+
     def render_match_image(self, frame1, frame2, matches, has_mp1=None, has_mp2=None):
         """Tracking::CreateCurrentMatchImage (Tracking.cc:899-940) -> uint8 [H, 2W, 3]."""
         a, b = self._image(frame1), self._image(frame2)
