@@ -1,4 +1,4 @@
-"""ctypes view of include/msf_abi.h and include/msf_initializer.h.  Loading fails loudly when libmsf.so is missing: there is no CPU fallback."""
+"""ctypes view of include/msf_abi.h, include/msf_initializer.h and include/msf_local_mapping.h.  Loading fails loudly when libmsf.so is missing: there is no CPU fallback."""
 import ctypes as C
 import os
 
@@ -47,6 +47,9 @@ ABI_SYMBOLS = ["msf_abi_version", "msf_default_config", "msf_create", "msf_destr
 # every symbol include/msf_initializer.h declares (a header and a version of its own: MSF_ABI_VERSION stays what it is)
 INITIALIZER_SYMBOLS = ["msf_initializer_version", "msf_reconstruct", "msf_reconstruct_device"]
 
+# every symbol include/msf_local_mapping.h declares (again a header and a version of its own)
+LOCAL_MAPPING_SYMBOLS = ["msf_local_mapping_version", "msf_new_points", "msf_new_points_device", "msf_create_map_points"]
+
 
 class Config(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_int32), ("device", C.c_int32), ("threshold", C.c_float),
@@ -84,6 +87,26 @@ class MotionResult(C.Structure):
                 ("cand_parallax", C.c_void_p), ("winner", C.c_void_p)]
 
 
+class View(C.Structure):
+    """msf_view: a key frame's pose and intrinsics"""
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float),
+                ("cx", C.c_float), ("cy", C.c_float)]
+
+
+class NewPointsParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("max_cos_parallax", C.c_double),
+                ("chi2", C.c_double)]
+
+
+class NewPointsResult(C.Structure):
+    """msf_new_points_result: host pointers for msf_new_points / msf_create_map_points, device pointers for
+    msf_new_points_device"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_new", C.c_void_p), ("packed", C.c_void_p),
+                ("status", C.c_void_p), ("points", C.c_void_p), ("hom", C.c_void_p), ("cos_parallax", C.c_void_p)]
+
+
+VIEW_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4")])
+NEW_POINT_DTYPE = np.dtype([("match", "<i4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4")])
 MATCH_DTYPE = np.dtype([("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4")])
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("response", "<f4"), ("angle", "<f4"),
                      ("octave", "<i4"), ("lx", "<i4"), ("ly", "<i4"), ("fast_score", "<i4")])
@@ -132,6 +155,12 @@ def load():
     L.msf_reconstruct.argtypes = [vp, i32, vp, i32, vp, vp, C.POINTER(MotionParams), C.POINTER(MotionResult)]
     L.msf_reconstruct_device.argtypes = [vp, i32, vp, i32, vp, i32, C.POINTER(RansacBatch), C.POINTER(MotionParams),
                                          C.POINTER(MotionResult), vp]
+    L.msf_local_mapping_version.restype = C.c_int
+    L.msf_new_points.argtypes = [vp, i32, vp, vp, vp, C.POINTER(NewPointsParams), C.POINTER(NewPointsResult)]
+    L.msf_new_points_device.argtypes = [vp, i32, vp, i32, vp, vp, vp, C.POINTER(NewPointsParams),
+                                        C.POINTER(NewPointsResult), vp]
+    L.msf_create_map_points.argtypes = [vp, i32, vp, i32, vp, vp, C.POINTER(NewPointsParams), vp, vp, i32,
+                                        C.POINTER(NewPointsResult)]
     L.msf_render_match_image.argtypes = [vp, C.POINTER(Image), C.POINTER(Image), vp, i32, vp, vp, vp, i64]
     L.msf_weights_info.argtypes = [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(i64)]
     L.msf_convert_weights.argtypes = [C.c_char_p, C.c_char_p]

@@ -10,7 +10,7 @@ SYNTH = os.path.join(_HERE, "libmsf_synth.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 HIP_SOURCES = ["msf_abi.cpp", "msf_multi.cpp", "msf_gather.cpp", "weights_io.cpp", "orb_kernels.hip", "loftr_kernels.hip", "pack_kernels.hip",
-               "ransac_kernels.hip", "reconstruct_kernels.hip"]
+               "ransac_kernels.hip", "reconstruct_kernels.hip", "triangulate_kernels.hip"]
 # -ffp-contract=off + correctly rounded f32 divide: the few f32 steps inside ORB
 # (Harris response, fastAtan2, pattern rotation) must round exactly like the CPU.
 # -mllvm -amdgpu-mfma-vgpr-form: MFMA results straight into VGPRs (the default put the accumulators of k_attn_update_x and
@@ -31,6 +31,7 @@ def _deps():
     d = [os.path.join(CSRC, f) for f in os.listdir(CSRC)]
     d.append(os.path.join(ROOT, "include", "msf_abi.h"))
     d.append(os.path.join(ROOT, "include", "msf_initializer.h"))
+    d.append(os.path.join(ROOT, "include", "msf_local_mapping.h"))
     return d
 
 

@@ -22,9 +22,12 @@
 
 namespace msf {
 
+#ifndef MSF_POINT3F_DEFINED   // hip_local_mapping.h has the same type
+#define MSF_POINT3F_DEFINED
 struct Point3f {   // cv::Point3f
   float x, y, z;
 };
+#endif
 
 namespace detail {
 // one device block, carved into 256-byte aligned pieces; freed on scope exit

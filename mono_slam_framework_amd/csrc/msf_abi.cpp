@@ -13,9 +13,11 @@
 
 #include "loftr_pipeline.h"
 #include "msf_initializer.h"
+#include "msf_local_mapping.h"
 #include "orb_pipeline.h"
 #include "ransac_solve.h"
 #include "reconstruct_pipeline.h"
+#include "triangulate_pipeline.h"
 #include "weights_io.h"
 
 namespace msf {
@@ -100,6 +102,10 @@ struct msf_handle {
   DevBuf<uint8_t> d_fm;
   // msf_reconstruct / msf_reconstruct_device workspace (candidates, counts, the host call's list and results), grown on demand
   DevBuf<uint8_t> d_rc;
+  // msf_new_points / msf_create_map_points workspace: the views, the results and the host call's list.  The first
+  // msf_create_map_points sizes it for max_batch_pairs lists of stage_cap matches; a longer msf_new_points list grows it.
+  DevBuf<uint8_t> d_lm;
+  std::vector<msf_view> view_stage;   // [2][n]: the query's view once per pair, then the neighbours'
   // msf_render_match_image workspace: the RGB image (allocated once) and the match list + flags (grown on demand)
   DevBuf<uint8_t> d_render;      // [H][2 * W][3]
   DevBuf<msf_match> d_render_m;  // [cap] matches, then 2 * cap flag bytes; cap = bytes / kRenderRecord
@@ -413,6 +419,32 @@ int fetch_single(msf_handle* h, msf_match* out, int32_t cap_per_pair, int32_t* n
   return capacity ? fail(h, MSF_ERR_CAPACITY, kNoResult) : MSF_OK;
 }
 
+// The front half of the one-vs-many entry points (msf_match_one_to_many, msf_create_map_points), n > 0.
+// one_to_many_args: the checks on the slots, with the entry point's name in front of the message.
+int one_to_many_args(msf_handle* h, const char* name, int32_t query_slot, int32_t n, const int32_t* slots) {
+  const int maxp = h->cfg.max_batch_pairs;
+  const std::string who = std::string(name) + ": ";
+  if (n > maxp) return fail(h, MSF_ERR_INVALID_ARG, who + "n exceeds max_batch_pairs");
+  if (!h->d_store) return fail(h, MSF_ERR_INVALID_ARG, who + "no frame was stored");
+  if (query_slot < 0 || query_slot >= 2 * maxp) return fail(h, MSF_ERR_INVALID_ARG, who + "bad query slot");
+  for (int i = 0; i < n; i++)
+    if (slots[i] < 0 || slots[i] >= 2 * maxp) return fail(h, MSF_ERR_INVALID_ARG, who + "bad slot");
+  return MSF_OK;
+}
+
+// launch_one_to_many: the slot arrays to the device (h->d_idx: query slot per pair, then train slot per pair), then the
+// match of the n pairs into the handle's lists h->d_out [n][stage_cap] and counts h->d_n [n].
+int launch_one_to_many(msf_handle* h, int32_t query_slot, int32_t n, const int32_t* slots, hipStream_t st) {
+  const int maxp = h->cfg.max_batch_pairs;
+  int32_t* d_query = h->d_idx;
+  int32_t* d_train = h->d_idx + maxp;
+  h->idx_stage.resize((size_t)2 * maxp);
+  for (int i = 0; i < n; i++) { h->idx_stage[i] = query_slot; h->idx_stage[maxp + i] = slots[i]; }
+  HIP_TRY(h, "hipMemcpyAsync(idx)",
+          hipMemcpyAsync(d_query, h->idx_stage.data(), (size_t)2 * maxp * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  return match_slot_pairs(h, n, d_query, d_train, h->d_out, h->stage_cap, h->d_n, st, 0);
+}
+
 // MatchFrames(a, b) through the frame cache: per frame a hash + byte compare on the host; only frames not seen lately
 // are uploaded and extracted; then one slot-pair match.  Same lists as the stateless path (tests/test_frame_cache_gpu.py).
 int match_pair_cached(msf_handle* h, const msf_image* a, const msf_image* b, msf_match* out, int32_t cap, int32_t* n_out,
@@ -702,31 +734,22 @@ int msf_store_frame(msf_handle* h, int32_t slot, const msf_image* img) {
 int msf_match_one_to_many(msf_handle* h, int32_t query_slot, int32_t n, const int32_t* slots, int32_t* num_matches,
                           int32_t* num_mp, msf_match* out, int32_t cap_per_pair) {
   return guarded(h, "msf_match_one_to_many", [&]() -> int {
-    const int maxp = h->cfg.max_batch_pairs;
+    const char* const name = "msf_match_one_to_many";
     if (n < 0 || (n > 0 && (!slots || !num_matches)) || (out && cap_per_pair < 1))
-      return fail(h, MSF_ERR_INVALID_ARG, "msf_match_one_to_many: bad argument");
+      return fail(h, MSF_ERR_INVALID_ARG, std::string(name) + ": bad argument");
     if (n == 0) return MSF_OK;
-    if (n > maxp) return fail(h, MSF_ERR_INVALID_ARG, "msf_match_one_to_many: n exceeds max_batch_pairs");
-    if (!h->d_store) return fail(h, MSF_ERR_INVALID_ARG, "msf_match_one_to_many: no frame was stored");
-    if (query_slot < 0 || query_slot >= 2 * maxp) return fail(h, MSF_ERR_INVALID_ARG, "msf_match_one_to_many: bad query slot");
-    for (int i = 0; i < n; i++)
-      if (slots[i] < 0 || slots[i] >= 2 * maxp) return fail(h, MSF_ERR_INVALID_ARG, "msf_match_one_to_many: bad slot");
+    if (int rc = one_to_many_args(h, name, query_slot, n, slots)) return rc;
     if (num_mp && !h->d_maps) return fail(h, MSF_ERR_INVALID_ARG, "msf_match_one_to_many: no map slot was ever set");
     CallScope cs{h};
     if (int rc = cs.enter()) return rc;
     hipStream_t st = cs.st;
-    int32_t* d_query = h->d_idx;
-    int32_t* d_train = h->d_idx + maxp;
-    int32_t* d_num_mp = h->d_idx + 2 * maxp;
-    h->idx_stage.resize((size_t)2 * maxp);
-    for (int i = 0; i < n; i++) { h->idx_stage[i] = query_slot; h->idx_stage[maxp + i] = slots[i]; }
-    HIP_TRY(h, "hipMemcpyAsync(idx)",
-            hipMemcpyAsync(d_query, h->idx_stage.data(), (size_t)2 * maxp * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if (int rc = match_slot_pairs(h, n, d_query, d_train, h->d_out, h->stage_cap, h->d_n, st, 0)) return rc;
+    if (int rc = launch_one_to_many(h, query_slot, n, slots, st)) return rc;
     if (num_mp) {
+      const int maxp = h->cfg.max_batch_pairs;
+      int32_t* d_num_mp = h->d_idx + 2 * maxp;
       HIP_TRY(h, "count_mappoint_matches",
-              msf::count_mappoint_matches(n, h->d_out, h->stage_cap, h->d_n, d_query, d_train, h->d_maps, h->n_maps,
-                                          h->map_words, h->cfg.image_width, h->cfg.image_height, d_num_mp, st));
+              msf::count_mappoint_matches(n, h->d_out, h->stage_cap, h->d_n, h->d_idx, h->d_idx + maxp, h->d_maps,
+                                          h->n_maps, h->map_words, h->cfg.image_width, h->cfg.image_height, d_num_mp, st));
       HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(num_mp, d_num_mp, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(num_matches, h->d_n, (size_t)n * 4, hipMemcpyDeviceToHost, st));
@@ -1091,6 +1114,178 @@ int msf_reconstruct_device(msf_handle* h, int32_t n_lists, const msf_match* d_ma
     }
     HIP_TRY(h, "reconstruct_motion", msf::reconstruct_motion(n_lists, in, motion_params(params), p.out, cs.st));
     return cs.finish();
+  });
+}
+
+namespace {
+
+// Where the host entry points of msf_local_mapping.h keep their device data: [lists] views of either side, every
+// output of the kernel with the lists' stride `cap`, and (with_list) one list of `cap` matches.
+struct NewPointsPlan {
+  msf::NewPointOut out{};
+  msf_view* view1 = nullptr;
+  msf_view* view2 = nullptr;
+  msf_match* matches = nullptr;
+};
+
+int plan_new_points(msf_handle* h, size_t lists, size_t cap, bool with_list, NewPointsPlan* p) {
+  size_t off = 0;
+  auto take = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
+  const size_t o_v1 = take(lists * sizeof(msf_view)), o_v2 = take(lists * sizeof(msf_view)), o_n = take(lists * 4);
+  const size_t o_packed = take(lists * cap * sizeof(msf_new_point)), o_status = take(lists * cap);
+  const size_t o_points = take(lists * cap * 12), o_hom = take(lists * cap * 16), o_cos = take(lists * cap * 8);
+  const size_t o_matches = with_list ? take(cap * sizeof(msf_match)) : 0;
+  if (off > h->d_lm.bytes) HIP_TRY(h, "hipMalloc(new points workspace)", h->d_lm.reserve(off, (size_t)1 << 16));
+  uint8_t* base = h->d_lm;
+  p->view1 = reinterpret_cast<msf_view*>(base + o_v1);
+  p->view2 = reinterpret_cast<msf_view*>(base + o_v2);
+  p->out.n_new = reinterpret_cast<int32_t*>(base + o_n);
+  p->out.packed = reinterpret_cast<msf_new_point*>(base + o_packed);
+  p->out.status = base + o_status;
+  p->out.points = reinterpret_cast<float*>(base + o_points);
+  p->out.hom = reinterpret_cast<float*>(base + o_hom);
+  p->out.cos_parallax = reinterpret_cast<double*>(base + o_cos);
+  p->matches = with_list ? reinterpret_cast<msf_match*>(base + o_matches) : nullptr;
+  return MSF_OK;
+}
+
+// the kernel writes only what somebody reads
+void keep_wanted(msf::NewPointOut* dev, const msf_new_points_result* wanted) {
+  if (!wanted->packed) dev->packed = nullptr;
+  if (!wanted->status) dev->status = nullptr;
+  if (!wanted->points) dev->points = nullptr;
+  if (!wanted->hom) dev->hom = nullptr;
+  if (!wanted->cos_parallax) dev->cos_parallax = nullptr;
+}
+
+// nullptr when params and out are usable, else what is wrong with them
+const char* new_points_fault(const msf_new_points_params* prm, const msf_new_points_result* out) {
+  if (!out || out->struct_size != sizeof(msf_new_points_result)) return "out is NULL or out->struct_size is not sizeof(msf_new_points_result)";
+  if (!prm || prm->struct_size != sizeof(msf_new_points_params)) return "params is NULL or params->struct_size is not sizeof(msf_new_points_params)";
+  if (std::isnan(prm->max_cos_parallax) || std::isnan(prm->chi2)) return "max_cos_parallax and chi2 must not be NaN";
+  if (!out->n_new) return "a required pointer is NULL (out->n_new)";
+  return nullptr;
+}
+
+// Rows [0, w) of list `i` of every wanted per-match array and the first n_new records, device stride dcap -> host
+// stride hcap, on `st`.
+int fetch_new_points(msf_handle* h, const msf::NewPointOut& dev, size_t dcap, const msf_new_points_result* out, size_t hcap,
+                     size_t i, size_t w, int32_t n_new, hipStream_t st) {
+  auto fetch = [&](void* dst, const void* src, size_t each, size_t count) {
+    return !dst || !count ? hipSuccess
+                          : hipMemcpyAsync(static_cast<uint8_t*>(dst) + i * hcap * each,
+                                           static_cast<const uint8_t*>(src) + i * dcap * each, count * each,
+                                           hipMemcpyDeviceToHost, st);
+  };
+  HIP_TRY(h, "hipMemcpyAsync", fetch(out->packed, dev.packed, sizeof(msf_new_point), n_new > 0 ? (size_t)n_new : 0));
+  HIP_TRY(h, "hipMemcpyAsync", fetch(out->status, dev.status, 1, w));
+  HIP_TRY(h, "hipMemcpyAsync", fetch(out->points, dev.points, 12, w));
+  HIP_TRY(h, "hipMemcpyAsync", fetch(out->hom, dev.hom, 16, w));
+  HIP_TRY(h, "hipMemcpyAsync", fetch(out->cos_parallax, dev.cos_parallax, 8, w));
+  return MSF_OK;
+}
+
+}  // namespace
+
+int msf_local_mapping_version(void) { return MSF_LOCAL_MAPPING_VERSION; }
+
+int msf_new_points(msf_handle* h, int32_t n_matches, const msf_match* matches, const msf_view* view1,
+                   const msf_view* view2, const msf_new_points_params* params, msf_new_points_result* out) {
+  return guarded(h, "msf_new_points", [&]() -> int {
+    if (const char* fault = new_points_fault(params, out))
+      return fail(h, MSF_ERR_INVALID_ARG, std::string("msf_new_points: ") + fault);
+    if (n_matches < 0) return fail(h, MSF_ERR_INVALID_ARG, "msf_new_points: n_matches is negative");
+    if (!view1 || !view2 || (n_matches > 0 && !matches))
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_new_points: a required pointer is NULL (matches, view1, view2)");
+    CallScope cs{h};
+    if (int rc = cs.enter()) return rc;
+    const int cap = n_matches > 0 ? n_matches : 1;
+    NewPointsPlan p;
+    if (int rc = plan_new_points(h, 1, (size_t)cap, true, &p)) return rc;
+    keep_wanted(&p.out, out);
+    hipStream_t st = cs.st;
+    Drain drain{st};
+    if (n_matches > 0)
+      HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.matches, matches, (size_t)n_matches * sizeof(msf_match), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.view1, view1, sizeof(msf_view), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.view2, view2, sizeof(msf_view), hipMemcpyHostToDevice, st));
+    const msf::NewPointLists in{p.matches, cap, cap, nullptr, n_matches, p.view1, p.view2};
+    HIP_TRY(h, "new_points", msf::new_points(1, in, msf::NewPointParams{params->max_cos_parallax, params->chi2}, p.out, st));
+    HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(out->n_new, p.out.n_new, 4, hipMemcpyDeviceToHost, st));
+    if (int rc = fetch_new_points(h, p.out, (size_t)cap, out, (size_t)cap, 0, (size_t)n_matches, 0, st)) return rc;
+    if (out->packed) {   // the first n_new records: the count has to arrive first
+      HIP_TRY(h, "hipStreamSynchronize", hipStreamSynchronize(st));
+      if (int rc = fetch_new_points(h, p.out, (size_t)cap, out, (size_t)cap, 0, 0, out->n_new[0], st)) return rc;
+    }
+    drain.armed = false;
+    return cs.finish();
+  });
+}
+
+int msf_new_points_device(msf_handle* h, int32_t n_lists, const msf_match* d_matches, int32_t cap_per_pair,
+                          const int32_t* d_n_out, const msf_view* d_view1, const msf_view* d_view2,
+                          const msf_new_points_params* params, msf_new_points_result* out, void* stream) {
+  return guarded(h, "msf_new_points_device", [&]() -> int {
+    if (const char* fault = new_points_fault(params, out))
+      return fail(h, MSF_ERR_INVALID_ARG, std::string("msf_new_points_device: ") + fault);
+    if (n_lists < 0 || n_lists > 65535)
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_new_points_device: n_lists outside [0, 65535]");
+    if (cap_per_pair < 1) return fail(h, MSF_ERR_INVALID_ARG, "msf_new_points_device: cap_per_pair < 1");
+    if (n_lists > 0 && (!d_matches || !d_n_out || !d_view1 || !d_view2))
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_new_points_device: a required pointer is NULL (d_matches, d_n_out, d_view1, d_view2)");
+    if (n_lists == 0) return MSF_OK;
+    CallScope cs{h};
+    if (int rc = cs.enter(stream)) return rc;
+    const msf::NewPointLists in{d_matches, cap_per_pair, cap_per_pair, d_n_out, 0, d_view1, d_view2};
+    const msf::NewPointOut dev{out->n_new, out->packed, out->status, out->points, out->hom, out->cos_parallax};
+    HIP_TRY(h, "new_points", msf::new_points(n_lists, in, msf::NewPointParams{params->max_cos_parallax, params->chi2}, dev, cs.st));
+    return cs.finish();
+  });
+}
+
+int msf_create_map_points(msf_handle* h, int32_t query_slot, const msf_view* query_view, int32_t n,
+                          const int32_t* slots, const msf_view* views, const msf_new_points_params* params,
+                          int32_t* num_matches, msf_match* out_matches, int32_t cap_per_pair,
+                          msf_new_points_result* out) {
+  return guarded(h, "msf_create_map_points", [&]() -> int {
+    const char* const name = "msf_create_map_points";
+    if (const char* fault = new_points_fault(params, out))
+      return fail(h, MSF_ERR_INVALID_ARG, std::string(name) + ": " + fault);
+    if (n < 0 || (n > 0 && (!slots || !num_matches || !query_view || !views)) || cap_per_pair < 1)
+      return fail(h, MSF_ERR_INVALID_ARG, std::string(name) + ": bad argument");
+    if (n == 0) return MSF_OK;
+    if (int rc = one_to_many_args(h, name, query_slot, n, slots)) return rc;
+    CallScope cs{h};
+    if (int rc = cs.enter()) return rc;
+    hipStream_t st = cs.st;
+    NewPointsPlan p;
+    if (int rc = plan_new_points(h, (size_t)h->cfg.max_batch_pairs, (size_t)h->stage_cap, false, &p)) return rc;
+    keep_wanted(&p.out, out);
+    Drain drain{st};
+    h->view_stage.resize((size_t)2 * n);
+    for (int i = 0; i < n; i++) { h->view_stage[i] = *query_view; h->view_stage[n + i] = views[i]; }
+    HIP_TRY(h, "hipMemcpyAsync(views)", hipMemcpyAsync(p.view1, h->view_stage.data(), (size_t)n * sizeof(msf_view), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, "hipMemcpyAsync(views)", hipMemcpyAsync(p.view2, h->view_stage.data() + n, (size_t)n * sizeof(msf_view), hipMemcpyHostToDevice, st));
+    if (int rc = launch_one_to_many(h, query_slot, n, slots, st)) return rc;
+    const int limit = cap_per_pair < h->stage_cap ? cap_per_pair : h->stage_cap;
+    const msf::NewPointLists in{h->d_out, h->stage_cap, limit, h->d_n, 0, p.view1, p.view2};
+    HIP_TRY(h, "new_points", msf::new_points(n, in, msf::NewPointParams{params->max_cos_parallax, params->chi2}, p.out, st));
+    HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(num_matches, h->d_n, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(out->n_new, p.out.n_new, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, "hipStreamSynchronize", hipStreamSynchronize(st));
+    // the copy-back: the counts say how much of every list there is to fetch
+    bool capacity = false;
+    for (int i = 0; i < n; i++) {
+      const int w = deliverable(h, num_matches[i], cap_per_pair, &capacity);
+      if (w > 0 && out_matches)
+        HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(out_matches + (size_t)i * cap_per_pair, h->d_out + (size_t)i * h->stage_cap,
+                                                    (size_t)w * sizeof(msf_match), hipMemcpyDeviceToHost, st));
+      if (int rc = fetch_new_points(h, p.out, (size_t)h->stage_cap, out, (size_t)cap_per_pair, (size_t)i, (size_t)w, out->n_new[i], st))
+        return rc;
+    }
+    drain.armed = false;
+    if (int rc = cs.finish()) return rc;
+    return capacity ? fail(h, MSF_ERR_CAPACITY, kNoResult) : MSF_OK;
   });
 }
 

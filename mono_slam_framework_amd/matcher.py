@@ -293,6 +293,117 @@ class _Matcher:
                                                    C.byref(batch), C.byref(prm), C.byref(res), stream))
         return d
 
+    @staticmethod
+    def make_views(views):
+        """views: a VIEW_DTYPE array or record, or an iterable of (Rcw [3, 3], tcw [3], fx, fy, cx, cy) -> VIEW_DTYPE [n]"""
+        if getattr(views, "dtype", None) == _lib.VIEW_DTYPE:
+            return np.ascontiguousarray(np.asarray(views).reshape(-1))
+        views = list(views)
+        out = np.zeros(len(views), _lib.VIEW_DTYPE)
+        for o, (R, t, fx, fy, cx, cy) in zip(out, views):
+            o["Rcw"] = np.asarray(R, np.float32).reshape(9)
+            o["tcw"] = np.asarray(t, np.float32).reshape(3)
+            o["fx"], o["fy"], o["cx"], o["cy"] = fx, fy, cx, cy
+        return out
+
+    @staticmethod
+    def _new_points_params(max_cos_parallax, chi2):
+        return _lib.NewPointsParams(struct_size=C.sizeof(_lib.NewPointsParams), max_cos_parallax=float(max_cos_parallax),
+                                    chi2=float(chi2))
+
+    @staticmethod
+    def _new_points_arrays(lists, cap):
+        return dict(n_new=np.zeros(lists, np.int32), packed=np.zeros((lists, cap), _lib.NEW_POINT_DTYPE),
+                    status=np.zeros((lists, cap), np.uint8), points=np.zeros((lists, cap, 3), np.float32),
+                    hom=np.zeros((lists, cap, 4), np.float32), cos_parallax=np.zeros((lists, cap), np.float64))
+
+    def new_points(self, matches, view1, view2, max_cos_parallax=1.1, chi2=5.991):
+        """The loop body of LocalMapping::CreateNewMapPoints (LocalMapping.cc:195-265) on one list: matches int32 [n, 4],
+        view1 / view2 one view each (see make_views).  -> dict: n_new, packed NEW_POINT_DTYPE [n_new] (match index and
+        x3D, in match order), status uint8 [n] (0 or the rejecting stage 1..7), points f32 [n, 3] (zero where rejected),
+        and the diagnostics hom f32 [n, 4], cos_parallax f64 [n]."""
+        m = np.ascontiguousarray(matches, np.int32).reshape(-1, 4)
+        n = len(m)
+        v1, v2 = self.make_views(view1), self.make_views(view2)
+        d = self._new_points_arrays(1, max(n, 1))
+        res = _lib.NewPointsResult(struct_size=C.sizeof(_lib.NewPointsResult))
+        for k, v in d.items():
+            setattr(res, k, v.ctypes.data)
+        prm = self._new_points_params(max_cos_parallax, chi2)
+        self._check(self._L.msf_new_points(self._h, n, m.ctypes.data, v1.ctypes.data, v2.ctypes.data, C.byref(prm),
+                                           C.byref(res)))
+        n_new = int(d["n_new"][0])
+        return dict(n_new=n_new, packed=d["packed"][0, :max(n_new, 0)], status=d["status"][0, :n], points=d["points"][0, :n],
+                    hom=d["hom"][0, :n], cos_parallax=d["cos_parallax"][0, :n])
+
+    def new_points_device(self, d_matches, d_n_out, d_view1, d_view2, max_cos_parallax=1.1, chi2=5.991, out=None,
+                          stream=None):
+        """The same for the lists of a batch in device memory (d_matches int32 [L, cap, 4], d_n_out int32 [L]) with the
+        views as CUDA uint8 tensors [L, 64] (torch.from_numpy(make_views(...).view(np.uint8)).cuda()).  -> dict of CUDA
+        tensors with a leading L: n_new int32, packed int32 [L, cap, 4] (match index, then the bits of x, y, z), status
+        uint8 [L, cap], points [L, cap, 3], hom [L, cap, 4], cos_parallax f64 [L, cap].  `out`: tensors to write into
+        instead of fresh zeros.  Asynchronous on `stream` (None = handle stream + sync)."""
+        import torch
+        assert d_matches.is_cuda and d_n_out.is_cuda and d_matches.is_contiguous() and d_n_out.is_contiguous()
+        assert d_matches.dtype == torch.int32 and d_n_out.dtype == torch.int32
+        L, cap = d_matches.shape[0], d_matches.shape[1]
+        for v in (d_view1, d_view2):
+            assert v.is_cuda and v.is_contiguous() and v.dtype == torch.uint8 and v.numel() == 64 * L
+        dev = d_matches.device
+        d = out
+        if d is None:
+            d = dict(n_new=torch.zeros((L,), dtype=torch.int32, device=dev),
+                     packed=torch.zeros((L, cap, 4), dtype=torch.int32, device=dev),
+                     status=torch.zeros((L, cap), dtype=torch.uint8, device=dev),
+                     points=torch.zeros((L, cap, 3), dtype=torch.float32, device=dev),
+                     hom=torch.zeros((L, cap, 4), dtype=torch.float32, device=dev),
+                     cos_parallax=torch.zeros((L, cap), dtype=torch.float64, device=dev))
+        res = _lib.NewPointsResult(struct_size=C.sizeof(_lib.NewPointsResult))
+        for k, v in d.items():
+            assert v.is_cuda and v.is_contiguous()
+            setattr(res, k, v.data_ptr())
+        prm = self._new_points_params(max_cos_parallax, chi2)
+        self._check(self._L.msf_new_points_device(self._h, L, d_matches.data_ptr(), cap, d_n_out.data_ptr(),
+                                                  d_view1.data_ptr(), d_view2.data_ptr(), C.byref(prm), C.byref(res), stream))
+        return d
+
+    def create_map_points(self, query_slot, query_view, slots, views, cap=4096, max_cos_parallax=1.1, chi2=5.991,
+                          diagnostics=False):
+        """LocalMapping::CreateNewMapPoints' loop (LocalMapping.cc:161-282) in one call: the stored frame query_slot is
+        matched against the stored frames `slots` and every match is triangulated from query_view and views[i].  The
+        baseline / median-depth gate stays with the caller: leave the neighbours it drops out of `slots`.
+        -> (num_matches [n], lists [n] of int32 [k, 4], new: list of dicts as new_points returns them; hom and
+        cos_parallax only with diagnostics=True)"""
+        slots = np.ascontiguousarray(np.asarray(slots, np.int32).reshape(-1))
+        n = slots.size
+        one = getattr(query_view, "dtype", None) == _lib.VIEW_DTYPE
+        qv, nv = self.make_views(query_view if one else [query_view]), self.make_views(views)
+        if len(qv) != 1 or len(nv) != n:
+            raise ValueError("one query view and one view per slot")
+        num = np.zeros(n, np.int32)
+        lists = np.zeros((n, cap), _lib.MATCH_DTYPE)
+        d = self._new_points_arrays(max(n, 1), cap)
+        if not diagnostics:
+            del d["hom"], d["cos_parallax"]
+        res = _lib.NewPointsResult(struct_size=C.sizeof(_lib.NewPointsResult))
+        for k, v in d.items():
+            setattr(res, k, v.ctypes.data)
+        prm = self._new_points_params(max_cos_parallax, chi2)
+        self._check(self._L.msf_create_map_points(self._h, query_slot, qv.ctypes.data, n, slots.ctypes.data,
+                                                  nv.ctypes.data, C.byref(prm), num.ctypes.data, lists.ctypes.data, cap,
+                                                  C.byref(res)))
+        out_lists, new = [], []
+        for i in range(n):
+            k = min(max(int(num[i]), 0), cap)
+            out_lists.append(lists[i, :k].view(np.int32).reshape(-1, 4).copy())
+            n_new = int(d["n_new"][i])
+            e = dict(n_new=n_new, packed=d["packed"][i, :max(n_new, 0)].copy(), status=d["status"][i, :k].copy(),
+                     points=d["points"][i, :k].copy())
+            if diagnostics:
+                e.update(hom=d["hom"][i, :k].copy(), cos_parallax=d["cos_parallax"][i, :k].copy())
+            new.append(e)
+        return num, out_lists, new
+
     def render_match_image(self, frame1, frame2, matches, has_mp1=None, has_mp2=None):
         """Tracking::CreateCurrentMatchImage (Tracking.cc:899-940) -> uint8 [H, 2W, 3]."""
         a, b = self._image(frame1), self._image(frame2)
