@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "carve.h"
 #include "loftr_pipeline.h"
 #include "msf_initializer.h"
 #include "msf_local_mapping.h"
@@ -93,11 +94,9 @@ struct msf_handle {
   DevBuf<uint8_t> d_store;
   DevBuf<int32_t> d_idx;         // [3][max_pairs]: query slot per pair, train slot per pair, map-point counts
   std::vector<int32_t> idx_stage;
-  // msf_check_hypotheses workspace, grown on demand
-  DevBuf<float> d_hyp;           // [2][hyp_cap][9] + [hyp_cap] scores
-  DevBuf<uint8_t> d_hyp_inl;     // [hyp_cap * hyp_match_cap]
-  DevBuf<msf_match> d_hyp_m;     // [hyp_match_cap]
-  int hyp_cap = 0, hyp_match_cap = 0;
+  // The geometry workspaces, one per family, each carved by that family's layout (carve()) and grown on demand.
+  // msf_check_hypotheses workspace (the two matrix arrays, scores, inlier flags, the list)
+  DevBuf<uint8_t> d_hyp;
   // msf_find_models / msf_find_models_device workspace (normalised points, sets, matrices, scores, ...), grown on demand
   DevBuf<uint8_t> d_fm;
   // msf_reconstruct / msf_reconstruct_device workspace (candidates, counts, the host call's list and results), grown on demand
@@ -206,6 +205,33 @@ struct Drain {
   bool armed = true;
   ~Drain() { if (armed) hipStreamSynchronize(s); }
 };
+
+// The workspace of one geometry call.  `layout` is a function of an msf::Carver& (carve.h) that fills the call's plan
+// struct; it runs on a null base to measure, `buf` grows to max(needed, floor) if it is too small (a failure is
+// MSF_ERR_HIP under `what`), then the same function runs on the block to place the pieces.
+template <class Layout>
+int carve(msf_handle* h, DevBuf<uint8_t>& buf, size_t floor, const char* what, Layout&& layout) {
+  msf::Carver measure;
+  layout(measure);
+  if (measure.off > buf.bytes) HIP_TRY(h, what, buf.reserve(measure.off, floor));
+  msf::Carver place{buf.p};
+  layout(place);
+  return MSF_OK;
+}
+
+// element `i` of an optional array: null stays null
+template <class T>
+T* from(T* p, size_t i) {
+  return p ? p + i : nullptr;
+}
+
+// The copy-back of the geometry host entry points, asynchronous on `st`: nothing to do when the caller gave no
+// pointer or there is nothing to copy.
+int fetch(msf_handle* h, hipStream_t st, void* dst, const void* src, size_t bytes) {
+  if (!dst || !bytes) return MSF_OK;
+  HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
+  return MSF_OK;
+}
 
 constexpr int kFrameCacheSlots = 64;   // default capacity of the transparent frame cache (MSF_FRAME_CACHE_SLOTS overrides)
 constexpr int kPinMatches = 1024;  // matches fetched together with the count by the single-pair call
@@ -760,6 +786,18 @@ int msf_match_one_to_many(msf_handle* h, int32_t query_slot, int32_t n, const in
   });
 }
 
+namespace {
+
+// The device arrays of one msf_check_hypotheses call, all pieces of the workspace: m21 / m12 [hc][9], scores [hc],
+// inliers [hc * mc] (the call indexes it with its own n_matches), matches [mc].
+struct HypothesesPlan {
+  float* m21 = nullptr, *m12 = nullptr, *scores = nullptr;
+  uint8_t* inliers = nullptr;
+  msf_match* matches = nullptr;
+};
+
+}  // namespace
+
 int msf_check_hypotheses(msf_handle* h, int32_t model, int32_t n_hyp, const float* m21, const float* m12,
                          int32_t n_matches, const msf_match* matches, float sigma, float* scores, int32_t* best,
                          uint8_t* best_inliers) {
@@ -774,33 +812,32 @@ int msf_check_hypotheses(msf_handle* h, int32_t model, int32_t n_hyp, const floa
     if (n_hyp == 0) return MSF_OK;
     CallScope cs{h};
     if (int rc = cs.enter()) return rc;
-    if (n_hyp > h->hyp_cap || n_matches > h->hyp_match_cap) {
-      h->hyp_cap = h->hyp_match_cap = 0;
-      const int hc = n_hyp > 256 ? n_hyp : 256, mc = n_matches > 2048 ? n_matches : 2048;
-      HIP_TRY(h, "hipMalloc", h->d_hyp.reserve((size_t)hc * 19 * sizeof(float)));
-      HIP_TRY(h, "hipMalloc", h->d_hyp_inl.reserve((size_t)hc * mc));
-      HIP_TRY(h, "hipMalloc", h->d_hyp_m.reserve((size_t)mc * sizeof(msf_match)));
-      h->hyp_cap = hc;
-      h->hyp_match_cap = mc;
-    }
+    // sized for at least 256 hypotheses and 2048 matches: no allocation in the steady state
+    const size_t hc = n_hyp > 256 ? n_hyp : 256, mc = n_matches > 2048 ? n_matches : 2048;
+    HypothesesPlan p;
+    if (int rc = carve(h, h->d_hyp, 0, "hipMalloc", [&](msf::Carver& c) {
+          p.m21 = c.take<float>(hc * 9);
+          p.m12 = c.take<float>(hc * 9);
+          p.scores = c.take<float>(hc);
+          p.inliers = c.take<uint8_t>(hc * mc);
+          p.matches = c.take<msf_match>(mc);
+        }))
+      return rc;
     hipStream_t st = cs.st;
     const size_t mat_bytes = (size_t)n_hyp * 9 * sizeof(float);
-    float* d21 = h->d_hyp;
-    float* d12 = h->d_hyp + (size_t)9 * h->hyp_cap;
-    float* dsc = h->d_hyp + (size_t)18 * h->hyp_cap;
-    HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(d21, m21, mat_bytes, hipMemcpyHostToDevice, st));
-    if (homography) HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(d12, m12, mat_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.m21, m21, mat_bytes, hipMemcpyHostToDevice, st));
+    if (homography) HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.m12, m12, mat_bytes, hipMemcpyHostToDevice, st));
     if (n_matches)
-      HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(h->d_hyp_m, matches, (size_t)n_matches * sizeof(msf_match), hipMemcpyHostToDevice, st));
-    HIP_TRY(h, "check_hypotheses", msf::check_hypotheses(model, n_hyp, d21, d12, n_matches, h->d_hyp_m, sigma, dsc, h->d_hyp_inl, st));
-    HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(scores, dsc, (size_t)n_hyp * sizeof(float), hipMemcpyDeviceToHost, st));
+      HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.matches, matches, (size_t)n_matches * sizeof(msf_match), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, "check_hypotheses", msf::check_hypotheses(model, n_hyp, p.m21, p.m12, n_matches, p.matches, sigma, p.scores, p.inliers, st));
+    if (int rc = fetch(h, st, scores, p.scores, (size_t)n_hyp * sizeof(float))) return rc;
     if (int rc = cs.finish()) return rc;
     // FindHomography / FindFundamental keep the first hypothesis whose score beats every earlier one (:190-194, :236-240)
     float score = 0.0f;
     for (int i = 0; i < n_hyp; i++)
       if (scores[i] > score) { score = scores[i]; *best = i; }
     if (*best >= 0 && n_matches)
-      HIP_TRY(h, "hipMemcpy", hipMemcpy(best_inliers, h->d_hyp_inl + (size_t)*best * n_matches, (size_t)n_matches, hipMemcpyDeviceToHost));
+      HIP_TRY(h, "hipMemcpy", hipMemcpy(best_inliers, p.inliers + (size_t)*best * n_matches, (size_t)n_matches, hipMemcpyDeviceToHost));
     return MSF_OK;
   });
 }
@@ -822,39 +859,22 @@ struct FindModelsPlan {
 // and every output get a piece of the workspace.  Returns MSF_OK or an error.
 int plan_find_models(msf_handle* h, int n_lists, int cap, int n_hyp, bool host_call, const msf_ransac_batch* user,
                      FindModelsPlan* p) {
-  size_t off = 0;
-  auto take = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
   const size_t L = (size_t)n_lists, LH = L * (size_t)n_hyp;
   const msf_ransac_result* res[2] = {&user->homography, &user->fundamental};
-  const size_t o_pn = take(L * cap * sizeof(float4)), o_T = take(L * 18 * sizeof(float));
-  const size_t o_sets = user->sets ? 0 : take(LH * 8 * sizeof(int32_t));
-  const size_t o_matches = host_call ? take((size_t)cap * sizeof(msf_match)) : 0;
-  size_t o_m21[2], o_aux[2], o_null[2], o_scores[2], o_best[2], o_inl[2];
-  for (int m = 0; m < 2; m++) {
-    float* user_aux = m == 0 ? res[m]->m12 : res[m]->fn;
-    o_m21[m] = res[m]->m21 ? 0 : take(LH * 9 * sizeof(float));
-    o_aux[m] = user_aux ? 0 : take(LH * 9 * sizeof(float));
-    o_null[m] = host_call ? take(LH * 9 * sizeof(float)) : 0;
-    o_scores[m] = res[m]->scores ? 0 : take((LH ? LH : 1) * sizeof(float));
-    o_best[m] = host_call ? take(sizeof(int32_t)) : 0;
-    o_inl[m] = host_call ? take((size_t)cap) : 0;
-  }
-  if (off > h->d_fm.bytes) HIP_TRY(h, "hipMalloc(find-models workspace)", h->d_fm.reserve(off, (size_t)1 << 20));
-  uint8_t* base = h->d_fm;
-  p->pn = reinterpret_cast<float4*>(base + o_pn);
-  p->T = reinterpret_cast<float*>(base + o_T);
-  p->sets = user->sets ? user->sets : reinterpret_cast<int32_t*>(base + o_sets);
-  p->matches = host_call ? reinterpret_cast<msf_match*>(base + o_matches) : nullptr;
-  for (int m = 0; m < 2; m++) {
-    float* user_aux = m == 0 ? res[m]->m12 : res[m]->fn;
-    p->m21[m] = res[m]->m21 ? res[m]->m21 : reinterpret_cast<float*>(base + o_m21[m]);
-    p->aux[m] = user_aux ? user_aux : reinterpret_cast<float*>(base + o_aux[m]);
-    p->null_vec[m] = host_call ? reinterpret_cast<float*>(base + o_null[m]) : res[m]->null_vec;
-    p->scores[m] = res[m]->scores ? res[m]->scores : reinterpret_cast<float*>(base + o_scores[m]);
-    p->best[m] = host_call ? reinterpret_cast<int32_t*>(base + o_best[m]) : res[m]->best;
-    p->inliers[m] = host_call ? base + o_inl[m] : res[m]->best_inliers;
-  }
-  return MSF_OK;
+  return carve(h, h->d_fm, (size_t)1 << 20, "hipMalloc(find-models workspace)", [&](msf::Carver& c) {
+    p->pn = c.take<float4>(L * cap);
+    p->T = c.take<float>(L * 18);
+    p->sets = c.take(user->sets, LH * 8);
+    p->matches = host_call ? c.take<msf_match>(cap) : nullptr;
+    for (int m = 0; m < 2; m++) {
+      p->m21[m] = c.take(res[m]->m21, LH * 9);
+      p->aux[m] = c.take(m == 0 ? res[m]->m12 : res[m]->fn, LH * 9);
+      p->null_vec[m] = host_call ? c.take<float>(LH * 9) : res[m]->null_vec;
+      p->scores[m] = c.take(res[m]->scores, LH ? LH : 1);
+      p->best[m] = host_call ? c.take<int32_t>(1) : res[m]->best;
+      p->inliers[m] = host_call ? c.take<uint8_t>(cap) : res[m]->best_inliers;
+    }
+  });
 }
 
 bool ransac_result_ok(const msf_ransac_result* r) {
@@ -894,18 +914,15 @@ int msf_find_models(msf_handle* h, int32_t n_matches, const msf_match* matches, 
     HIP_TRY(h, "find_models", msf::find_models(1, p.matches, n_matches, nullptr, n_matches, n_hyp, p.sets, sigma, p.pn, p.T, p.m21,
                                                p.aux, p.null_vec, p.scores, p.best, p.inliers, st));
     const size_t mat_bytes = (size_t)n_hyp * 9 * sizeof(float);
-    auto fetch = [&](void* dst, const void* src, size_t bytes) {
-      return !dst || !bytes ? hipSuccess : hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
-    };
     for (int m = 0; m < 2; m++) {
-      HIP_TRY(h, "hipMemcpyAsync", fetch(res[m]->m21, p.m21[m], mat_bytes));
-      HIP_TRY(h, "hipMemcpyAsync", fetch(m == 0 ? res[m]->m12 : res[m]->fn, p.aux[m], mat_bytes));
-      HIP_TRY(h, "hipMemcpyAsync", fetch(res[m]->null_vec, p.null_vec[m], mat_bytes));
-      HIP_TRY(h, "hipMemcpyAsync", fetch(res[m]->scores, p.scores[m], (size_t)n_hyp * sizeof(float)));
-      HIP_TRY(h, "hipMemcpyAsync", fetch(res[m]->best, p.best[m], sizeof(int32_t)));
-      HIP_TRY(h, "hipMemcpyAsync", fetch(res[m]->best_inliers, p.inliers[m], (size_t)n_matches));
-      HIP_TRY(h, "hipMemcpyAsync", fetch(res[m]->T1, p.T, 9 * sizeof(float)));
-      HIP_TRY(h, "hipMemcpyAsync", fetch(res[m]->T2, p.T + 9, 9 * sizeof(float)));
+      if (int rc = fetch(h, st, res[m]->m21, p.m21[m], mat_bytes)) return rc;
+      if (int rc = fetch(h, st, m == 0 ? res[m]->m12 : res[m]->fn, p.aux[m], mat_bytes)) return rc;
+      if (int rc = fetch(h, st, res[m]->null_vec, p.null_vec[m], mat_bytes)) return rc;
+      if (int rc = fetch(h, st, res[m]->scores, p.scores[m], (size_t)n_hyp * sizeof(float))) return rc;
+      if (int rc = fetch(h, st, res[m]->best, p.best[m], sizeof(int32_t))) return rc;
+      if (int rc = fetch(h, st, res[m]->best_inliers, p.inliers[m], (size_t)n_matches)) return rc;
+      if (int rc = fetch(h, st, res[m]->T1, p.T, 9 * sizeof(float))) return rc;
+      if (int rc = fetch(h, st, res[m]->T2, p.T + 9, 9 * sizeof(float))) return rc;
     }
     drain.armed = false;
     return cs.finish();   // the one wait of the call
@@ -954,41 +971,27 @@ struct ReconstructPlan {
 // workspace for every output, the list included).  points / triangulated are only produced where somebody reads them.
 int plan_reconstruct(msf_handle* h, int n_lists, int cap, bool host_call, const msf_motion_result* user,
                      const msf_motion_result* wanted, ReconstructPlan* p) {
-  size_t off = 0;
-  auto take = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
   const size_t L = (size_t)n_lists;
-  auto piece = [&](const void* given, size_t bytes) { return given ? (size_t)0 : take(bytes); };
-  const size_t o_ok = piece(user->ok, L * 4), o_model = piece(user->model, L * 4), o_ninl = take(L * 4);
-  const size_t o_ncand = piece(user->n_cand, L * 4), o_cr = piece(user->cand_R, L * 72 * 4);
-  const size_t o_ct = piece(user->cand_t, L * 24 * 4), o_cg = piece(user->cand_good, L * 8 * 4);
-  const size_t o_cp = piece(user->cand_parallax, L * 8 * 4), o_win = piece(user->winner, L * 4);
-  const size_t o_R = piece(user->R21, L * 9 * 4), o_t = piece(user->t21, L * 3 * 4);
   const bool want_points = host_call && wanted->points, want_tri = host_call && wanted->triangulated;
-  const size_t o_pts = want_points ? take(L * cap * 12) : 0, o_tri = want_tri ? take(L * cap) : 0;
-  const size_t o_matches = host_call ? take((size_t)cap * sizeof(msf_match)) : 0;
-  const size_t o_inl = host_call ? take((size_t)cap) : 0, o_m21 = host_call ? take(9 * 4) : 0;
-  if (off > h->d_rc.bytes) HIP_TRY(h, "hipMalloc(reconstruct workspace)", h->d_rc.reserve(off, (size_t)1 << 16));
-  uint8_t* base = h->d_rc;
-  auto at = [&](auto* given, size_t o) { return given ? given : reinterpret_cast<decltype(given)>(base + o); };
-  p->out.ok = at(user->ok, o_ok);
-  p->out.model = at(user->model, o_model);
-  p->out.n_inliers = reinterpret_cast<int32_t*>(base + o_ninl);
-  p->out.n_cand = at(user->n_cand, o_ncand);
-  p->out.cand_R = at(user->cand_R, o_cr);
-  p->out.cand_t = at(user->cand_t, o_ct);
-  p->out.cand_good = at(user->cand_good, o_cg);
-  p->out.cand_parallax = at(user->cand_parallax, o_cp);
-  p->out.winner = at(user->winner, o_win);
-  p->out.R21 = at(user->R21, o_R);
-  p->out.t21 = at(user->t21, o_t);
-  p->out.points = host_call ? (want_points ? reinterpret_cast<float*>(base + o_pts) : nullptr) : user->points;
-  p->out.triangulated = host_call ? (want_tri ? base + o_tri : nullptr) : user->triangulated;
-  if (host_call) {
-    p->matches = reinterpret_cast<msf_match*>(base + o_matches);
-    p->inliers = base + o_inl;
-    p->m21 = reinterpret_cast<float*>(base + o_m21);
-  }
-  return MSF_OK;
+  return carve(h, h->d_rc, (size_t)1 << 16, "hipMalloc(reconstruct workspace)", [&](msf::Carver& c) {
+    msf::MotionOut& o = p->out;
+    o.ok = c.take(user->ok, L);
+    o.model = c.take(user->model, L);
+    o.n_inliers = c.take<int32_t>(L);
+    o.n_cand = c.take(user->n_cand, L);
+    o.cand_R = c.take(user->cand_R, L * 72);
+    o.cand_t = c.take(user->cand_t, L * 24);
+    o.cand_good = c.take(user->cand_good, L * 8);
+    o.cand_parallax = c.take(user->cand_parallax, L * 8);
+    o.winner = c.take(user->winner, L);
+    o.R21 = c.take(user->R21, L * 9);
+    o.t21 = c.take(user->t21, L * 3);
+    o.points = !host_call ? user->points : want_points ? c.take<float>(L * cap * 3) : nullptr;
+    o.triangulated = !host_call ? user->triangulated : want_tri ? c.take<uint8_t>(L * cap) : nullptr;
+    p->matches = host_call ? c.take<msf_match>(cap) : nullptr;
+    p->inliers = host_call ? c.take<uint8_t>(cap) : nullptr;
+    p->m21 = host_call ? c.take<float>(9) : nullptr;
+  });
 }
 
 // nullptr when the parameters are usable, else what is wrong with them
@@ -1013,6 +1016,10 @@ msf::MotionParams motion_params(const msf_motion_params* prm) {
   d.min_triangulated = prm->min_triangulated;
   d.min_parallax = prm->min_parallax;
   return d;
+}
+
+msf::NewPointParams new_point_params(const msf_new_points_params* prm) {
+  return msf::NewPointParams{prm->max_cos_parallax, prm->chi2};
 }
 
 }  // namespace
@@ -1054,21 +1061,18 @@ int msf_reconstruct(msf_handle* h, int32_t model, const float* m21, int32_t n_ma
     in.m21[model] = p.m21;
     in.inliers[model] = p.inliers;
     HIP_TRY(h, "reconstruct_motion", msf::reconstruct_motion(1, in, motion_params(params), p.out, st));
-    auto fetch = [&](void* dst, const void* src, size_t bytes) {
-      return !dst || !bytes ? hipSuccess : hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
-    };
-    HIP_TRY(h, "hipMemcpyAsync", fetch(out->ok, p.out.ok, 4));
-    HIP_TRY(h, "hipMemcpyAsync", fetch(out->model, p.out.model, 4));
-    HIP_TRY(h, "hipMemcpyAsync", fetch(out->R21, p.out.R21, 9 * 4));
-    HIP_TRY(h, "hipMemcpyAsync", fetch(out->t21, p.out.t21, 3 * 4));
-    HIP_TRY(h, "hipMemcpyAsync", fetch(out->points, p.out.points, (size_t)n_matches * 12));
-    HIP_TRY(h, "hipMemcpyAsync", fetch(out->triangulated, p.out.triangulated, (size_t)n_matches));
-    HIP_TRY(h, "hipMemcpyAsync", fetch(out->n_cand, p.out.n_cand, 4));
-    HIP_TRY(h, "hipMemcpyAsync", fetch(out->cand_R, p.out.cand_R, 72 * 4));
-    HIP_TRY(h, "hipMemcpyAsync", fetch(out->cand_t, p.out.cand_t, 24 * 4));
-    HIP_TRY(h, "hipMemcpyAsync", fetch(out->cand_good, p.out.cand_good, 8 * 4));
-    HIP_TRY(h, "hipMemcpyAsync", fetch(out->cand_parallax, p.out.cand_parallax, 8 * 4));
-    HIP_TRY(h, "hipMemcpyAsync", fetch(out->winner, p.out.winner, 4));
+    if (int rc = fetch(h, st, out->ok, p.out.ok, 4)) return rc;
+    if (int rc = fetch(h, st, out->model, p.out.model, 4)) return rc;
+    if (int rc = fetch(h, st, out->R21, p.out.R21, 9 * 4)) return rc;
+    if (int rc = fetch(h, st, out->t21, p.out.t21, 3 * 4)) return rc;
+    if (int rc = fetch(h, st, out->points, p.out.points, (size_t)n_matches * 12)) return rc;
+    if (int rc = fetch(h, st, out->triangulated, p.out.triangulated, (size_t)n_matches)) return rc;
+    if (int rc = fetch(h, st, out->n_cand, p.out.n_cand, 4)) return rc;
+    if (int rc = fetch(h, st, out->cand_R, p.out.cand_R, 72 * 4)) return rc;
+    if (int rc = fetch(h, st, out->cand_t, p.out.cand_t, 24 * 4)) return rc;
+    if (int rc = fetch(h, st, out->cand_good, p.out.cand_good, 8 * 4)) return rc;
+    if (int rc = fetch(h, st, out->cand_parallax, p.out.cand_parallax, 8 * 4)) return rc;
+    if (int rc = fetch(h, st, out->winner, p.out.winner, 4)) return rc;
     drain.armed = false;
     return cs.finish();   // the one wait of the call
   });
@@ -1129,24 +1133,17 @@ struct NewPointsPlan {
 };
 
 int plan_new_points(msf_handle* h, size_t lists, size_t cap, bool with_list, NewPointsPlan* p) {
-  size_t off = 0;
-  auto take = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
-  const size_t o_v1 = take(lists * sizeof(msf_view)), o_v2 = take(lists * sizeof(msf_view)), o_n = take(lists * 4);
-  const size_t o_packed = take(lists * cap * sizeof(msf_new_point)), o_status = take(lists * cap);
-  const size_t o_points = take(lists * cap * 12), o_hom = take(lists * cap * 16), o_cos = take(lists * cap * 8);
-  const size_t o_matches = with_list ? take(cap * sizeof(msf_match)) : 0;
-  if (off > h->d_lm.bytes) HIP_TRY(h, "hipMalloc(new points workspace)", h->d_lm.reserve(off, (size_t)1 << 16));
-  uint8_t* base = h->d_lm;
-  p->view1 = reinterpret_cast<msf_view*>(base + o_v1);
-  p->view2 = reinterpret_cast<msf_view*>(base + o_v2);
-  p->out.n_new = reinterpret_cast<int32_t*>(base + o_n);
-  p->out.packed = reinterpret_cast<msf_new_point*>(base + o_packed);
-  p->out.status = base + o_status;
-  p->out.points = reinterpret_cast<float*>(base + o_points);
-  p->out.hom = reinterpret_cast<float*>(base + o_hom);
-  p->out.cos_parallax = reinterpret_cast<double*>(base + o_cos);
-  p->matches = with_list ? reinterpret_cast<msf_match*>(base + o_matches) : nullptr;
-  return MSF_OK;
+  return carve(h, h->d_lm, (size_t)1 << 16, "hipMalloc(new points workspace)", [&](msf::Carver& c) {
+    p->view1 = c.take<msf_view>(lists);
+    p->view2 = c.take<msf_view>(lists);
+    p->out.n_new = c.take<int32_t>(lists);
+    p->out.packed = c.take<msf_new_point>(lists * cap);
+    p->out.status = c.take<uint8_t>(lists * cap);
+    p->out.points = c.take<float>(lists * cap * 3);
+    p->out.hom = c.take<float>(lists * cap * 4);
+    p->out.cos_parallax = c.take<double>(lists * cap);
+    p->matches = with_list ? c.take<msf_match>(cap) : nullptr;
+  });
 }
 
 // the kernel writes only what somebody reads
@@ -1171,17 +1168,12 @@ const char* new_points_fault(const msf_new_points_params* prm, const msf_new_poi
 // stride hcap, on `st`.
 int fetch_new_points(msf_handle* h, const msf::NewPointOut& dev, size_t dcap, const msf_new_points_result* out, size_t hcap,
                      size_t i, size_t w, int32_t n_new, hipStream_t st) {
-  auto fetch = [&](void* dst, const void* src, size_t each, size_t count) {
-    return !dst || !count ? hipSuccess
-                          : hipMemcpyAsync(static_cast<uint8_t*>(dst) + i * hcap * each,
-                                           static_cast<const uint8_t*>(src) + i * dcap * each, count * each,
-                                           hipMemcpyDeviceToHost, st);
-  };
-  HIP_TRY(h, "hipMemcpyAsync", fetch(out->packed, dev.packed, sizeof(msf_new_point), n_new > 0 ? (size_t)n_new : 0));
-  HIP_TRY(h, "hipMemcpyAsync", fetch(out->status, dev.status, 1, w));
-  HIP_TRY(h, "hipMemcpyAsync", fetch(out->points, dev.points, 12, w));
-  HIP_TRY(h, "hipMemcpyAsync", fetch(out->hom, dev.hom, 16, w));
-  HIP_TRY(h, "hipMemcpyAsync", fetch(out->cos_parallax, dev.cos_parallax, 8, w));
+  const size_t hi = i * hcap, di = i * dcap, records = n_new > 0 ? (size_t)n_new : 0;
+  if (int rc = fetch(h, st, from(out->packed, hi), from(dev.packed, di), records * sizeof(msf_new_point))) return rc;
+  if (int rc = fetch(h, st, from(out->status, hi), from(dev.status, di), w)) return rc;
+  if (int rc = fetch(h, st, from(out->points, hi * 3), from(dev.points, di * 3), w * 12)) return rc;
+  if (int rc = fetch(h, st, from(out->hom, hi * 4), from(dev.hom, di * 4), w * 16)) return rc;
+  if (int rc = fetch(h, st, from(out->cos_parallax, hi), from(dev.cos_parallax, di), w * 8)) return rc;
   return MSF_OK;
 }
 
@@ -1210,8 +1202,8 @@ int msf_new_points(msf_handle* h, int32_t n_matches, const msf_match* matches, c
     HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.view1, view1, sizeof(msf_view), hipMemcpyHostToDevice, st));
     HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.view2, view2, sizeof(msf_view), hipMemcpyHostToDevice, st));
     const msf::NewPointLists in{p.matches, cap, cap, nullptr, n_matches, p.view1, p.view2};
-    HIP_TRY(h, "new_points", msf::new_points(1, in, msf::NewPointParams{params->max_cos_parallax, params->chi2}, p.out, st));
-    HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(out->n_new, p.out.n_new, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, "new_points", msf::new_points(1, in, new_point_params(params), p.out, st));
+    if (int rc = fetch(h, st, out->n_new, p.out.n_new, 4)) return rc;
     if (int rc = fetch_new_points(h, p.out, (size_t)cap, out, (size_t)cap, 0, (size_t)n_matches, 0, st)) return rc;
     if (out->packed) {   // the first n_new records: the count has to arrive first
       HIP_TRY(h, "hipStreamSynchronize", hipStreamSynchronize(st));
@@ -1238,7 +1230,7 @@ int msf_new_points_device(msf_handle* h, int32_t n_lists, const msf_match* d_mat
     if (int rc = cs.enter(stream)) return rc;
     const msf::NewPointLists in{d_matches, cap_per_pair, cap_per_pair, d_n_out, 0, d_view1, d_view2};
     const msf::NewPointOut dev{out->n_new, out->packed, out->status, out->points, out->hom, out->cos_parallax};
-    HIP_TRY(h, "new_points", msf::new_points(n_lists, in, msf::NewPointParams{params->max_cos_parallax, params->chi2}, dev, cs.st));
+    HIP_TRY(h, "new_points", msf::new_points(n_lists, in, new_point_params(params), dev, cs.st));
     return cs.finish();
   });
 }
@@ -1269,17 +1261,17 @@ int msf_create_map_points(msf_handle* h, int32_t query_slot, const msf_view* que
     if (int rc = launch_one_to_many(h, query_slot, n, slots, st)) return rc;
     const int limit = cap_per_pair < h->stage_cap ? cap_per_pair : h->stage_cap;
     const msf::NewPointLists in{h->d_out, h->stage_cap, limit, h->d_n, 0, p.view1, p.view2};
-    HIP_TRY(h, "new_points", msf::new_points(n, in, msf::NewPointParams{params->max_cos_parallax, params->chi2}, p.out, st));
-    HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(num_matches, h->d_n, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(out->n_new, p.out.n_new, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, "new_points", msf::new_points(n, in, new_point_params(params), p.out, st));
+    if (int rc = fetch(h, st, num_matches, h->d_n, (size_t)n * 4)) return rc;
+    if (int rc = fetch(h, st, out->n_new, p.out.n_new, (size_t)n * 4)) return rc;
     HIP_TRY(h, "hipStreamSynchronize", hipStreamSynchronize(st));
     // the copy-back: the counts say how much of every list there is to fetch
     bool capacity = false;
     for (int i = 0; i < n; i++) {
       const int w = deliverable(h, num_matches[i], cap_per_pair, &capacity);
-      if (w > 0 && out_matches)
-        HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(out_matches + (size_t)i * cap_per_pair, h->d_out + (size_t)i * h->stage_cap,
-                                                    (size_t)w * sizeof(msf_match), hipMemcpyDeviceToHost, st));
+      if (int rc = fetch(h, st, from(out_matches, (size_t)i * cap_per_pair), h->d_out + (size_t)i * h->stage_cap,
+                         (size_t)w * sizeof(msf_match)))
+        return rc;
       if (int rc = fetch_new_points(h, p.out, (size_t)h->stage_cap, out, (size_t)cap_per_pair, (size_t)i, (size_t)w, out->n_new[i], st))
         return rc;
     }

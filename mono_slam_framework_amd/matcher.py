@@ -22,6 +22,33 @@ class MsfError(RuntimeError):
         self.code = code
 
 
+def _fill(res, arrays):
+    """Points the result struct `res` at `arrays` (field name -> numpy array or contiguous CUDA tensor) and sets its
+    struct_size.  -> res"""
+    res.struct_size = C.sizeof(type(res))
+    for k, v in arrays.items():
+        if isinstance(v, np.ndarray):
+            setattr(res, k, v.ctypes.data)
+        else:
+            assert v.is_cuda and v.is_contiguous()
+            setattr(res, k, v.data_ptr())
+    return res
+
+
+def _device_lists(d_matches, d_n_out):
+    """The lists of a batch in device memory, as every *_device wrapper takes them -> (n_lists, cap, device)"""
+    import torch
+    assert d_matches.is_cuda and d_n_out.is_cuda and d_matches.is_contiguous() and d_n_out.is_contiguous()
+    assert d_matches.dtype == torch.int32 and d_n_out.dtype == torch.int32
+    return d_matches.shape[0], d_matches.shape[1], d_matches.device
+
+
+def _zeros_on(dev):
+    """-> z(shape, dtype="float32"): a tensor of zeros on `dev`"""
+    import torch
+    return lambda shape, dtype="float32": torch.zeros(shape, dtype=getattr(torch, dtype), device=dev)
+
+
 class _Matcher:
     _kind = None
 
@@ -181,11 +208,8 @@ class _Matcher:
                      best_inliers=np.zeros(max(n, 1), np.uint8), T1=np.zeros((3, 3), np.float32),
                      T2=np.zeros((3, 3), np.float32))
             d["m12" if name == "H" else "fn"] = np.zeros((n_hyp, 3, 3), np.float32)
-            r = _lib.RansacResult(struct_size=C.sizeof(_lib.RansacResult))
-            for k, v in d.items():
-                setattr(r, k, v.ctypes.data)
             out[name] = d
-            res.append(r)
+            res.append(_fill(_lib.RansacResult(), d))
         self._check(self._L.msf_find_models(self._h, n, m.ctypes.data, n_hyp, sets.ctypes.data, float(sigma),
                                             C.byref(res[0]), C.byref(res[1])))
         for d in out.values():
@@ -200,24 +224,16 @@ class _Matcher:
         (keys as find_models; best int32 [n_lists], best_inliers uint8 [n_lists, cap]).  Lists shorter than 8 or longer
         than 8192 get best = -1.  Asynchronous on `stream` (None = handle stream + sync)."""
         import torch
-        assert d_matches.is_cuda and d_n_out.is_cuda and d_matches.is_contiguous() and d_n_out.is_contiguous()
-        assert d_matches.dtype == torch.int32 and d_n_out.dtype == torch.int32
-        L, cap = d_matches.shape[0], d_matches.shape[1]
-        dev = d_matches.device
-
-        def z(shape, dtype=torch.float32):
-            return torch.zeros(shape, dtype=dtype, device=dev)
-
-        out = {"sets": z((L, n_hyp, 8), torch.int32)}
-        batch = _lib.RansacBatch(struct_size=C.sizeof(_lib.RansacBatch), sets=out["sets"].data_ptr())
+        L, cap, dev = _device_lists(d_matches, d_n_out)
+        z = _zeros_on(dev)
+        out = {"sets": z((L, n_hyp, 8), "int32")}
+        batch = _fill(_lib.RansacBatch(), {"sets": out["sets"]})
         for name, r in (("H", batch.homography), ("F", batch.fundamental)):
             d = dict(m21=z((L, n_hyp, 3, 3)), null_vec=z((L, n_hyp, 3, 3)), scores=z((L, n_hyp)),
-                     best=torch.full((L,), -1, dtype=torch.int32, device=dev), best_inliers=z((L, cap), torch.uint8),
+                     best=torch.full((L,), -1, dtype=torch.int32, device=dev), best_inliers=z((L, cap), "uint8"),
                      T1=z((L, 3, 3)), T2=z((L, 3, 3)))
             d["m12" if name == "H" else "fn"] = z((L, n_hyp, 3, 3))
-            r.struct_size = C.sizeof(_lib.RansacResult)
-            for k, v in d.items():
-                setattr(r, k, v.data_ptr())
+            _fill(r, d)
             out[name] = d
         self._check(self._L.msf_find_models_device(self._h, L, d_matches.data_ptr(), cap, d_n_out.data_ptr(), n_hyp,
                                                    int(seed), float(sigma), C.byref(batch), stream))
@@ -246,9 +262,7 @@ class _Matcher:
                  triangulated=np.zeros(max(n, 1), np.uint8), n_cand=np.zeros(1, np.int32),
                  cand_R=np.zeros((8, 3, 3), np.float32), cand_t=np.zeros((8, 3), np.float32),
                  cand_good=np.zeros(8, np.int32), cand_parallax=np.zeros(8, np.float32), winner=np.zeros(1, np.int32))
-        res = _lib.MotionResult(struct_size=C.sizeof(_lib.MotionResult))
-        for k, v in d.items():
-            setattr(res, k, v.ctypes.data)
+        res = _fill(_lib.MotionResult(), d)
         prm = self._motion_params(K, sigma, min_triangulated, min_parallax)
         self._check(self._L.msf_reconstruct(self._h, int(model), m21.ctypes.data, n, m.ctypes.data, inl.ctypes.data,
                                             C.byref(prm), C.byref(res)))
@@ -264,30 +278,18 @@ class _Matcher:
         find_models_device returned for the same d_matches / d_n_out; H or F is chosen per list by RH.
         -> dict of CUDA tensors with a leading n_lists dimension (keys as reconstruct; points [n_lists, cap, 3],
         triangulated uint8 [n_lists, cap]).  Asynchronous on `stream` (None = handle stream + sync)."""
-        import torch
-        assert d_matches.is_cuda and d_n_out.is_cuda and d_matches.is_contiguous() and d_n_out.is_contiguous()
-        assert d_matches.dtype == torch.int32 and d_n_out.dtype == torch.int32
-        L, cap = d_matches.shape[0], d_matches.shape[1]
-        dev = d_matches.device
+        L, cap, dev = _device_lists(d_matches, d_n_out)
         n_hyp = found["H"]["scores"].shape[1]
-        batch = _lib.RansacBatch(struct_size=C.sizeof(_lib.RansacBatch), sets=found["sets"].data_ptr())
+        batch = _fill(_lib.RansacBatch(), {"sets": found["sets"]})
         for name, r in (("H", batch.homography), ("F", batch.fundamental)):
-            r.struct_size = C.sizeof(_lib.RansacResult)
-            for k in ("m21", "scores", "best", "best_inliers"):
-                t = found[name][k]
-                assert t.is_cuda and t.is_contiguous() and t.shape[0] == L
-                setattr(r, k, t.data_ptr())
-
-        def z(shape, dtype=torch.float32):
-            return torch.zeros(shape, dtype=dtype, device=dev)
-
-        i32 = torch.int32
+            given = {k: found[name][k] for k in ("m21", "scores", "best", "best_inliers")}
+            assert all(t.shape[0] == L for t in given.values())
+            _fill(r, given)
+        z, i32 = _zeros_on(dev), "int32"
         d = dict(ok=z((L,), i32), model=z((L,), i32), R21=z((L, 3, 3)), t21=z((L, 3)), points=z((L, cap, 3)),
-                 triangulated=z((L, cap), torch.uint8), n_cand=z((L,), i32), cand_R=z((L, 8, 3, 3)), cand_t=z((L, 8, 3)),
+                 triangulated=z((L, cap), "uint8"), n_cand=z((L,), i32), cand_R=z((L, 8, 3, 3)), cand_t=z((L, 8, 3)),
                  cand_good=z((L, 8), i32), cand_parallax=z((L, 8)), winner=z((L,), i32))
-        res = _lib.MotionResult(struct_size=C.sizeof(_lib.MotionResult))
-        for k, v in d.items():
-            setattr(res, k, v.data_ptr())
+        res = _fill(_lib.MotionResult(), d)
         prm = self._motion_params(K, sigma, min_triangulated, min_parallax)
         self._check(self._L.msf_reconstruct_device(self._h, L, d_matches.data_ptr(), cap, d_n_out.data_ptr(), n_hyp,
                                                    C.byref(batch), C.byref(prm), C.byref(res), stream))
@@ -326,9 +328,7 @@ class _Matcher:
         n = len(m)
         v1, v2 = self.make_views(view1), self.make_views(view2)
         d = self._new_points_arrays(1, max(n, 1))
-        res = _lib.NewPointsResult(struct_size=C.sizeof(_lib.NewPointsResult))
-        for k, v in d.items():
-            setattr(res, k, v.ctypes.data)
+        res = _fill(_lib.NewPointsResult(), d)
         prm = self._new_points_params(max_cos_parallax, chi2)
         self._check(self._L.msf_new_points(self._h, n, m.ctypes.data, v1.ctypes.data, v2.ctypes.data, C.byref(prm),
                                            C.byref(res)))
@@ -344,24 +344,15 @@ class _Matcher:
         uint8 [L, cap], points [L, cap, 3], hom [L, cap, 4], cos_parallax f64 [L, cap].  `out`: tensors to write into
         instead of fresh zeros.  Asynchronous on `stream` (None = handle stream + sync)."""
         import torch
-        assert d_matches.is_cuda and d_n_out.is_cuda and d_matches.is_contiguous() and d_n_out.is_contiguous()
-        assert d_matches.dtype == torch.int32 and d_n_out.dtype == torch.int32
-        L, cap = d_matches.shape[0], d_matches.shape[1]
+        L, cap, dev = _device_lists(d_matches, d_n_out)
         for v in (d_view1, d_view2):
             assert v.is_cuda and v.is_contiguous() and v.dtype == torch.uint8 and v.numel() == 64 * L
-        dev = d_matches.device
         d = out
         if d is None:
-            d = dict(n_new=torch.zeros((L,), dtype=torch.int32, device=dev),
-                     packed=torch.zeros((L, cap, 4), dtype=torch.int32, device=dev),
-                     status=torch.zeros((L, cap), dtype=torch.uint8, device=dev),
-                     points=torch.zeros((L, cap, 3), dtype=torch.float32, device=dev),
-                     hom=torch.zeros((L, cap, 4), dtype=torch.float32, device=dev),
-                     cos_parallax=torch.zeros((L, cap), dtype=torch.float64, device=dev))
-        res = _lib.NewPointsResult(struct_size=C.sizeof(_lib.NewPointsResult))
-        for k, v in d.items():
-            assert v.is_cuda and v.is_contiguous()
-            setattr(res, k, v.data_ptr())
+            z = _zeros_on(dev)
+            d = dict(n_new=z((L,), "int32"), packed=z((L, cap, 4), "int32"), status=z((L, cap), "uint8"),
+                     points=z((L, cap, 3)), hom=z((L, cap, 4)), cos_parallax=z((L, cap), "float64"))
+        res = _fill(_lib.NewPointsResult(), d)
         prm = self._new_points_params(max_cos_parallax, chi2)
         self._check(self._L.msf_new_points_device(self._h, L, d_matches.data_ptr(), cap, d_n_out.data_ptr(),
                                                   d_view1.data_ptr(), d_view2.data_ptr(), C.byref(prm), C.byref(res), stream))
@@ -385,9 +376,7 @@ class _Matcher:
         d = self._new_points_arrays(max(n, 1), cap)
         if not diagnostics:
             del d["hom"], d["cos_parallax"]
-        res = _lib.NewPointsResult(struct_size=C.sizeof(_lib.NewPointsResult))
-        for k, v in d.items():
-            setattr(res, k, v.ctypes.data)
+        res = _fill(_lib.NewPointsResult(), d)
         prm = self._new_points_params(max_cos_parallax, chi2)
         self._check(self._L.msf_create_map_points(self._h, query_slot, qv.ctypes.data, n, slots.ctypes.data,
                                                   nv.ctypes.data, C.byref(prm), num.ctypes.data, lists.ctypes.data, cap,

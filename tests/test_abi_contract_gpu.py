@@ -406,9 +406,9 @@ def _translations(n_hyp, seed):
 
 
 def test_workspaces_grow_and_keep_working(orb):
-    """msf_check_hypotheses, msf_render_match_image and msf_find_models each with a small call, one above the floor of
-    its grow-on-demand workspace (256 hypotheses / 2048 matches; 4096 matches; 1 MiB), and the small call again: the
-    first and the third result are identical, and the large one is right"""
+    """msf_check_hypotheses, msf_render_match_image, msf_find_models, msf_reconstruct and msf_new_points each with a
+    small call, one above the floor of its grow-on-demand workspace (256 hypotheses / 2048 matches; 4096 matches; 1 MiB;
+    64 KiB; 64 KiB), and the small call again: the first and the third result are identical, and the large one is right"""
     # msf_check_hypotheses: 8 / 16, 300 / 2100, 8 / 16
     small_m, big_m = _scene(16, 1), _scene(2100, 2)
     small_h, big_h = _translations(8, 3), _translations(300, 4)
@@ -454,3 +454,50 @@ def test_workspaces_grow_and_keep_working(orb):
     f4 = orb.find_models(lst, np.concatenate([sets_small, sets_big[:5992]]), 1.0)
     for name in ("H", "F"):
         np.testing.assert_array_equal(f4[name]["m21"][:8].view(np.uint32), f1[name]["m21"].view(np.uint32))
+
+    # msf_reconstruct: about 30 bytes of workspace per match with points and flags wanted, so 8192 matches pass 64 KiB
+    from tests import initializer_ref as ir
+    c1, c3 = ir.case("planar", 1), ir.case("planar", 3)
+    reps = -(-8192 // len(c3["matches"]))                # test_reconstruct_gpu.big_list: planar 3 tiled, +-1 px jitter
+    big_m = np.concatenate([c3["matches"]] * reps)[:8192].copy()
+    big_m[:, 2:] += np.random.RandomState(11).randint(-1, 2, (8192, 2))
+    big_inl = np.concatenate([c3["H"]["inliers"]] * reps)[:8192]
+    r1 = orb.reconstruct(0, c1["H"]["m21"], c1["matches"], c1["H"]["inliers"], ir.K)
+    r2 = orb.reconstruct(0, c3["H"]["m21"], big_m, big_inl, ir.K)
+    r3 = orb.reconstruct(0, c1["H"]["m21"], c1["matches"], c1["H"]["inliers"], ir.K)
+    assert set(r1) == set(r3) and len(r1["points"]) == 300
+    for key, v in r1.items():
+        np.testing.assert_array_equal(np.atleast_1d(v).view(np.uint8), np.atleast_1d(r3[key]).view(np.uint8), err_msg=key)
+    ir.check_result(ir.reconstruct(0, c3["H"]["m21"], big_m, big_inl), r2, big_m, big_inl, label="8192 matches")
+    assert r2["ok"] == 1 and r2["cand_good"][r2["winner"]] > 4000
+
+    # msf_new_points: 69 bytes of workspace per match, so 4096 matches pass 64 KiB
+    from tests import local_mapping_ref as lm
+    view1, views2, lists = lm.scene(1)
+    tile = lists[0]
+    n, whole, rest = len(tile), 4096 // len(tile), 4096 % len(tile)
+    assert whole >= 2 and rest > 0
+    big_m = np.concatenate([tile] * (whole + 1))[:4096]
+    n1 = orb.new_points(tile, view1, views2[0])
+    n2 = orb.new_points(big_m, view1, views2[0])
+    n3 = orb.new_points(tile, view1, views2[0])
+    keys = ("status", "points", "hom", "cos_parallax", "packed")
+    assert set(n1) == set(keys) | {"n_new"} and 0 < n1["n_new"] < n and len(n1["status"]) == n
+    assert n1["n_new"] == n3["n_new"]
+    for key in keys:
+        np.testing.assert_array_equal(n1[key].view(np.uint8), n3[key].view(np.uint8), err_msg=key)
+    # a match's result does not depend on its neighbours in the list: every tile repeats the small call's rows
+    for t in range(whole + 1):
+        k = n if t < whole else rest
+        for key in keys[:4]:
+            np.testing.assert_array_equal(n2[key][t * n:t * n + k].view(np.uint8), n1[key][:k].view(np.uint8),
+                                          err_msg="tile %d %s" % (t, key))
+    accepted = np.flatnonzero(n1["status"] == 0)
+    assert n1["n_new"] == len(accepted)
+    assert n2["n_new"] == whole * n1["n_new"] + int((accepted < rest).sum()) == len(n2["packed"])
+    # the records: in match order, the accepted matches of every tile with the small call's points
+    want = np.concatenate([n1["packed"][accepted < (n if t < whole else rest)] for t in range(whole + 1)])
+    at = np.concatenate([accepted[accepted < (n if t < whole else rest)] + t * n for t in range(whole + 1)])
+    np.testing.assert_array_equal(n2["packed"]["match"], at)
+    for axis in "xyz":
+        np.testing.assert_array_equal(n2["packed"][axis].view(np.uint32), want[axis].view(np.uint32), err_msg=axis)
