@@ -387,7 +387,8 @@ typedef enum msf_debug_what {
   MSF_DBG_WALK_MODE = 10,    /* ORB, int32 [2]: {1 if the handle launches the pyramid + FAST walker level by level (after a
                                 stalled one-launch walker, or MSF_ORB_WALK_PER_LEVEL=1), else 0; units of one-launch
                                 walkers that gave up a bounded wait since msf_create} -- see "Walker stall" below */
-  MSF_DBG_LOFTR_ACT = 9,     /* float NCHW activation of the first frame of the last backbone pass after ResNet stage
+  MSF_DBG_LOFTR_ACT = 9,     /* float NCHW activation of one frame of the last backbone pass (the first; msf_debug_loftr_backbone: image
+                                act_image) after ResNet stage
                                 `level` + 1: [8][240][320], [16][120][160], [32][60][80], [32][30][40] (level 0..3) */
   MSF_DBG_LOFTR_TOK = 11     /* float [2][1200][32] tokens of pair 0 before the transformer (backbone + positional
                                 encoding) of the last match call; MSF_FLAG_KEEP_DEBUG handles only */
@@ -414,6 +415,19 @@ int msf_debug_loftr_head(msf_handle* h, int32_t n_pairs, const float* d_feat0, c
  * n_blocks < 1, first_block + n_blocks > 8, a pointer not 16-byte aligned.  Not timed by msf_stage_times. */
 int msf_debug_loftr_transformer(msf_handle* h, int32_t n_pairs, int32_t first_block, int32_t n_blocks,
                                 const float* d_in0, const float* d_in1, float* d_out0, float* d_out1, void* stream);
+
+/* LoFTR: the ResNet backbone alone (ConvertImageToFloat, 21 convolutions, positional encoding), in ONE backbone pass of
+ * the two forms a handle makes: n frames from d_a and n from d_b (a match call), or, with d_b null, n frames from d_a (an
+ * extract call; d_tok_b is then ignored).  Frames, strides and alignment as msf_match_batch_device.  d_tok_a / d_tok_b:
+ * device float [n][1200][32], the tokens before the transformer (the layout of MSF_DBG_LOFTR_TOK).  The kernels are those
+ * a match call of that many images takes on this handle: MSF_FLAG_LOFTR_F32, the backbone switches read at msf_create,
+ * and the streaming kernels from 64 images on.  With MSF_FLAG_KEEP_DEBUG the four layer activations of image act_image of
+ * the pass (0 <= act_image < n or 2 n; the A frames come first) are kept for msf_debug_get(MSF_DBG_LOFTR_ACT); match
+ * calls keep image 0.  MSF_ERR_INVALID_ARG for an ORB handle, n < 0 or above the handle's backbone chunk
+ * (min(max_batch_pairs, 256)), act_image out of range, a pointer or stride not 16-byte aligned, row_stride < image_width,
+ * frames that overlap.  n = 0 does nothing.  Not timed by msf_stage_times. */
+int msf_debug_loftr_backbone(msf_handle* h, int32_t n, const uint8_t* d_a, const uint8_t* d_b, int64_t frame_stride,
+                             int64_t row_stride, int32_t act_image, float* d_tok_a, float* d_tok_b, void* stream);
 
 /* per-stage device time, measured with HIP events on the launch stream (needs MSF_FLAG_PROFILE): the SUM over the batch
  * calls since the previous query -- queried after every call it is that call's times; a caller that enqueues many calls

@@ -4235,7 +4235,6 @@ struct LoftrPipeline::Impl {
   bool dense_head = false;
   bool fuse_blocks = true;   // MSF_LOFTR_UNFUSED=1: one kernel per convolution (tests: bit-identical results)
   bool split_bf16 = true;    // MSF_LOFTR_F32=1: every convolution on the f32 MFMA (no split-bf16 kernels)
-  bool down_stream = true;   // MSF_LOFTR_DOWN=0: layer2's first block as two kernels instead of the streaming k_down16x
   int strip_min_images = 64; // backbone passes of fewer images use the banded kernels (run_backbone)
   int strip_mode = 3;        // MSF_LOFTR_STRIP: non-zero (default) = the streaming strip kernels (stem + block 1 in one pass,
                              // then block 2, ...); 0 = the banded kernels calls of fewer than 64 images take anyway
@@ -4247,6 +4246,7 @@ struct LoftrPipeline::Impl {
   bool act_split[4] = {false, false, false, false};           // ... kept in the streaming kernels' split-pixel format (debug_get converts)
   int dbg_pair = 0;
   bool have_dbg = false;
+  bool have_act = false;     // a backbone pass has kept its activations (act_dbg)
   // Stage events (start, backbone done, transformer done, head done) as a ring of sets: a call records into the next free
   // set and nobody waits, so a caller can enqueue batches ahead of the device; stage_times() harvests the finished sets
   // and returns the sums since the last query (a query after every call sees that call's times, as before)
@@ -4327,7 +4327,6 @@ std::string LoftrPipeline::init(const char* weights_path, int max_pairs, bool pr
     P.split_bf16 = !f32_convs;
     if (const char* d = getenv("MSF_LOFTR_F32")) P.split_bf16 = atoi(d) == 0;
     if (const char* d = getenv("MSF_LOFTR_STRIP")) P.strip_mode = atoi(d);
-    if (const char* d = getenv("MSF_LOFTR_DOWN")) P.down_stream = atoi(d) != 0;
     if (const char* d = getenv("MSF_LOFTR_STRIP_MIN")) P.strip_min_images = atoi(d);   // tests: strips for a single pair
     // pairs per backbone pass (activation working set: 19.7 MB per pair).  Whole launches of 512 images fill the 512
     // workgroup slots of the fused block kernels in whole rounds (64 pairs: conv stack 8.41 ms, 128: 8.15, 256: 8.07)
@@ -4873,8 +4872,9 @@ namespace {
 // Backbone (ConvertImageToFloat + 21 convs + positional encoding) for one chunk of images: nA frames from srcA
 // followed by nB frames from srcB (either may be 0); their tokens go to tokA / tokB.  A frame's tokens do not depend
 // on the frame it is paired with, which is what the per-frame token cache below rests on.
+// act_image: the image of the pass (A frames first, then B) whose four layer activations MSF_FLAG_KEEP_DEBUG keeps.
 void run_backbone(LoftrPipeline::Impl& P, const uint8_t* srcA, int nA, float* tokA, const uint8_t* srcB, int nB,
-                  float* tokB, long long frame_stride, int row_stride, hipStream_t st);
+                  float* tokB, long long frame_stride, int row_stride, hipStream_t st, int act_image = 0);
 
 }  // namespace
 
@@ -4932,10 +4932,25 @@ hipError_t LoftrPipeline::match_slots(int n_pairs, const int32_t* d_slot_a, cons
 
 int LoftrPipeline::max_slots() const { return p_ ? p_->n_slots : 0; }
 
+int LoftrPipeline::backbone_chunk() const { return p_ ? p_->chunk : 0; }
+
+// msf_debug_loftr_backbone: one backbone pass in one of the two forms production makes (match(): n + n images, extract():
+// n + 0), with the kernels run_backbone chooses for this handle and that many images; the tokens go to the caller
+hipError_t LoftrPipeline::backbone_only(int n, const uint8_t* d_a, const uint8_t* d_b, long long frame_stride,
+                                        int row_stride, int act_image, float* d_tok_a, float* d_tok_b, hipStream_t st) {
+  if (!p_) return hipErrorNotInitialized;
+  Impl& P = *p_;
+  const int nB = d_b ? n : 0;
+  if (n < 0 || n > P.chunk || act_image < 0 || (n > 0 && act_image >= n + nB)) return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  run_backbone(P, d_a, n, d_tok_a, d_b, nB, d_tok_b, frame_stride, row_stride, st, act_image);
+  return hipGetLastError();
+}
+
 namespace {
 
 void run_backbone(LoftrPipeline::Impl& P, const uint8_t* srcA, int nA, float* tokA, const uint8_t* srcB, int nB,
-                  float* tokB, long long frame_stride, int row_stride, hipStream_t st) {
+                  float* tokB, long long frame_stride, int row_stride, hipStream_t st, int act_image) {
   const int ni = nA + nB;
   const ConvDesc* c = P.conv;
   float *a = P.bufA, *b = P.bufB, *cc = P.bufC, *d = P.bufD;
@@ -4944,8 +4959,10 @@ void run_backbone(LoftrPipeline::Impl& P, const uint8_t* srcA, int nA, float* to
   // A streaming workgroup walks a whole 240-row strip (~70 us however few images there are): calls of fewer than 64
   // images -- the single-pair drop-in path -- keep the short banded workgroups (stateless pair: 0.84 vs 1.06 ms).
   const int strip_mode = ni >= P.strip_min_images ? P.strip_mode : 0;
-  const bool stem_fused = P.fuse_blocks && P.split_bf16 && strip_mode != 0;   // stem + block 1 in one pass -> cc
-  if (stem_fused) {
+  // the streaming kernels hand split pixels to each other (layers 1, 2 and the first block of layer 3), so they run all
+  // or none: stem + block 1 in one pass -> cc, then one pass per block
+  const bool streaming = P.fuse_blocks && P.split_bf16 && strip_mode != 0;
+  if (streaming) {
     launch_stem_strip8x(c, srcA, nA, srcB, nB, frame_stride, row_stride, cc, st);
   } else {
     if (nA) launch_conv<1, 8, 7, 2, 64, true, false, true, 2>(c[0], srcA, frame_stride, row_stride, nullptr, a, nA, st);
@@ -4953,7 +4970,7 @@ void run_backbone(LoftrPipeline::Impl& P, const uint8_t* srcA, int nA, float* to
   }
   // layer1 @240x320, 8 ch
   if (P.fuse_blocks) {   // each BasicBlock in one kernel: the intermediate activation stays in LDS
-    if (stem_fused) {
+    if (streaming) {
       launch_strip8x(c + 3, cc, a, ni, st);                                                          // a = 196
     } else if (P.split_bf16) {
       launch_block8x(c[1], c[2], a, cc, ni, st);
@@ -4968,42 +4985,43 @@ void run_backbone(LoftrPipeline::Impl& P, const uint8_t* srcA, int nA, float* to
     launch_conv<8, 8, 3, 1, 64, true, false, false, 2>(c[3], cc, s8, 0, nullptr, b, ni, st);
     launch_conv<8, 8, 3, 1, 64, true, true, false, 2>(c[4], b, s8, 0, cc, a, ni, st);                 // a = 196
   }
-  // MSF_FLAG_KEEP_DEBUG: the first image's activation (raw bytes; `split`: in the streaming kernels' split-pixel format)
+  // MSF_FLAG_KEEP_DEBUG: image act_image's activation (raw bytes; `split`: in the streaming kernels' split-pixel format,
+  // whose image stride in bytes is that of f32 NCHW)
   auto keep = [&](int l, const float* src, size_t elems, bool split) {
     if (P.act_dbg[l]) {
-      hipMemcpyAsync(P.act_dbg[l], src, elems * sizeof(float), hipMemcpyDeviceToDevice, st);
+      hipMemcpyAsync(P.act_dbg[l], src + (size_t)act_image * elems, elems * sizeof(float), hipMemcpyDeviceToDevice, st);
       P.act_split[l] = split;
+      P.have_act = true;
     }
   };
-  keep(0, a, 8u * 240 * 320, P.fuse_blocks && stem_fused);
+  keep(0, a, 8u * 240 * 320, streaming);
   // layer2 @120x160, 16 ch
   const long long s16 = 16LL * 120 * 160;
-  if (P.fuse_blocks && P.split_bf16 && strip_mode != 0 && P.down_stream) {
+  if (streaming) {
     launch_down16x(c[5], c[7], c[6], a, cc, ni, st);                                               // cc = 205
   } else {
     launch_conv<8, 16, 3, 2, 32, true, false, false, 1, true>(c[5], a, s8, 0, nullptr, b, ni, st, &c[7], d);   // + shortcut -> d
     launch_conv<16, 16, 3, 1, 32, true, true, false>(c[6], b, s16, 0, d, cc, ni, st);              // cc = 205
   }
   if (P.fuse_blocks) {
-    if (P.split_bf16 && strip_mode != 0 && P.down_stream) launch_strip16x(c[8], c[9], cc, a, ni, st);   // a = 212
+    if (streaming) launch_strip16x(c[8], c[9], cc, a, ni, st);   // a = 212
     else if (P.split_bf16) launch_block16x(c[8], c[9], cc, a, ni, st);
     else launch_block16(c[8], c[9], cc, a, ni, st);
   } else {
     launch_conv<16, 16, 3, 1, 32, true, false, false>(c[8], cc, s16, 0, nullptr, b, ni, st);
     launch_conv<16, 16, 3, 1, 32, true, true, false>(c[9], b, s16, 0, cc, a, ni, st);              // a = 212
   }
-  keep(1, a, 16u * 120 * 160, P.fuse_blocks && P.split_bf16 && strip_mode != 0 && P.down_stream);
+  keep(1, a, 16u * 120 * 160, streaming);
   // layer3 @60x80, 32 ch
   const long long s32 = 32LL * 60 * 80;
-  const bool down3 = P.split_bf16 && P.fuse_blocks && strip_mode != 0 && P.down_stream;
-  if (down3) launch_down32x(c[10], c[12], c[11], a, cc, ni, st);                                   // cc = 221
+  if (streaming) launch_down32x(c[10], c[12], c[11], a, cc, ni, st);                               // cc = 221
   else if (P.split_bf16) launch_convx2<16>(c[10], c[12], a, b, d, ni, st);
   else launch_conv<16, 32, 3, 2, 16, true, false, false, 1, true>(c[10], a, s16, 0, nullptr, b, ni, st, &c[12], d);
   if (P.split_bf16) {
-    if (!down3) launch_convx<32, true>(c[11], b, d, cc, ni, st);                                   // cc = 221
-    if (strip_mode != 0 && P.down_stream) {
+    if (streaming) {   // k_strip32x reads k_down32x's split pixels
       launch_strip32x(c[13], c[14], cc, a, ni, st);                                                // a = 228
     } else {
+      launch_convx<32, true>(c[11], b, d, cc, ni, st);                                             // cc = 221
       launch_convx<32, false>(c[13], cc, nullptr, b, ni, st);
       launch_convx<32, true>(c[14], b, cc, a, ni, st);                                             // a = 228
     }
@@ -5236,7 +5254,7 @@ int LoftrPipeline::stage_times(const char** names, float* ms, int cap) {
 
 int LoftrPipeline::debug_get(int what, int slot, int level, void* host_out, size_t cap, size_t* n_bytes,
                              std::string* err) {
-  if (!p_ || !p_->have_dbg) { *err = "no LoFTR batch has run yet, or the handle was created without MSF_FLAG_KEEP_DEBUG"; return MSF_ERR_INVALID_ARG; }
+  if (!p_ || !(p_->have_dbg || (what == MSF_DBG_LOFTR_ACT && p_->have_act))) { *err = "no LoFTR batch has run yet, or the handle was created without MSF_FLAG_KEEP_DEBUG"; return MSF_ERR_INVALID_ARG; }
   if (slot != 0) { *err = "LoFTR debug tensors are kept for pair 0 of the last call only"; return MSF_ERR_INVALID_ARG; }
   if (hipDeviceSynchronize() != hipSuccess) { *err = "hipDeviceSynchronize failed"; return MSF_ERR_HIP; }
   const float* src = nullptr;

@@ -40,6 +40,13 @@ class LoftrPipeline {
   // arguments as match() (a layer pair's self-attention blocks share a launch when both are in the range); not timed
   hipError_t transformer_only(int n_pairs, int first, int n_blocks, const float* d_in0, const float* d_in1, float* d_out0,
                               float* d_out1, hipStream_t st);
+  // the backbone alone (msf_debug_loftr_backbone): ONE pass of n frames from d_a and, when d_b is not null, n from d_b --
+  // the two forms match() and extract() make -- with the kernels a match call of that many images takes on this handle;
+  // tokens to d_tok_a / d_tok_b ([n][1200][32] each); with keep_debug the four layer activations of image act_image of
+  // the pass (A frames first) are kept for debug_get; n at most backbone_chunk(); not timed
+  hipError_t backbone_only(int n, const uint8_t* d_a, const uint8_t* d_b, long long frame_stride, int row_stride,
+                           int act_image, float* d_tok_a, float* d_tok_b, hipStream_t st);
+  int backbone_chunk() const;   // pairs per backbone pass
   int max_slots() const;
   int debug_get(int what, int slot, int level, void* host_out, size_t cap, size_t* n_bytes, std::string* err);
   int stage_times(const char** names, float* ms, int cap);

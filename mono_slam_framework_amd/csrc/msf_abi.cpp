@@ -1366,6 +1366,28 @@ int msf_debug_loftr_transformer(msf_handle* h, int32_t n_pairs, int32_t first_bl
   });
 }
 
+int msf_debug_loftr_backbone(msf_handle* h, int32_t n, const uint8_t* d_a, const uint8_t* d_b, int64_t frame_stride,
+                             int64_t row_stride, int32_t act_image, float* d_tok_a, float* d_tok_b, void* stream) {
+  return guarded(h, "msf_debug_loftr_backbone", [&]() -> int {
+    if (h->cfg.kind != MSF_KIND_LOFTR) return fail(h, MSF_ERR_INVALID_ARG, "msf_debug_loftr_backbone: not a LoFTR handle");
+    const int images = d_b ? 2 * n : n;
+    if (n < 0 || n > h->loftr.backbone_chunk() || !d_a || !d_tok_a || (d_b && !d_tok_b) || act_image < 0 ||
+        (n > 0 && act_image >= images))
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_debug_loftr_backbone: bad argument");
+    if (!aligned16(d_a, d_b, frame_stride, row_stride, d_tok_a, d_tok_b))
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_debug_loftr_backbone: misaligned pointer");
+    if (row_stride < h->cfg.image_width) return fail(h, MSF_ERR_INVALID_ARG, "row_stride < image_width");
+    if (frame_stride < row_stride * (long long)h->cfg.image_height)
+      return fail(h, MSF_ERR_INVALID_ARG, "frame_stride < row_stride * image_height (frames would overlap)");
+    if (n == 0) return MSF_OK;
+    CallScope cs{h};
+    if (int rc = cs.enter(stream)) return rc;
+    HIP_TRY(h, "loftr backbone", h->loftr.backbone_only(n, d_a, d_b, frame_stride, (int)row_stride, act_image, d_tok_a,
+                                                        d_tok_b, cs.st));
+    return cs.finish();
+  });
+}
+
 int msf_stage_times(msf_handle* h, const char** names, float* ms, int32_t cap) {
   if (!names || !ms || cap < 1) return 0;
   const int n = guarded(h, "msf_stage_times", [&]() -> int {

@@ -544,6 +544,27 @@ class DNNFeatureMatcher(_Matcher):
         self._check(self._L.msf_debug_loftr_head(self._h, n, d_f0.data_ptr(), d_f1.data_ptr(), d_out.data_ptr(),
                                                  d_out.shape[1], d_n_out.data_ptr(), stream))
 
+    def backbone_device(self, d_a, d_b, d_tok_a, d_tok_b, act_image=0, frame_stride=None, row_stride=None, n=None,
+                        stream=None):
+        """The ResNet backbone alone (msf_debug_loftr_backbone), one backbone pass: d_a uint8 CUDA frames, n of them;
+        d_b the same or None (the extract form; d_tok_b may then be None too).  Dense [n, 480, 640] frames by default,
+        else `n` frames `frame_stride` bytes apart with rows `row_stride` bytes apart.  d_tok_a / d_tok_b: float32
+        CUDA tensors [n, 1200, 32], written with the tokens before the transformer.  With MSF_FLAG_KEEP_DEBUG
+        backbone_activation() then returns image `act_image` of the pass (A frames first).  Asynchronous on `stream`
+        (an int hipStream_t; None = handle stream + sync)."""
+        import torch
+        if n is None:
+            n = d_a.shape[0]
+        row_stride = self.width if row_stride is None else row_stride
+        frame_stride = row_stride * self.height if frame_stride is None else frame_stride
+        for t in (d_a, d_b):
+            assert t is None or (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.numel() >= n * frame_stride)
+        for t in (d_tok_a,) + ((d_tok_b,) if d_b is not None else ()):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (n, 1200, 32)
+        self._check(self._L.msf_debug_loftr_backbone(self._h, n, d_a.data_ptr(), None if d_b is None else d_b.data_ptr(),
+                                                     frame_stride, row_stride, act_image, d_tok_a.data_ptr(),
+                                                     None if d_tok_b is None or d_b is None else d_tok_b.data_ptr(), stream))
+
     def backbone_activation(self, stage):
         """NCHW activation of the first frame of the last call after ResNet stage `stage` + 1 (MSF_FLAG_KEEP_DEBUG)"""
         shape = [(8, 240, 320), (16, 120, 160), (32, 60, 80), (32, 30, 40)][stage]

@@ -96,6 +96,7 @@ def test_null_handle(orb):
         "msf_debug_get": lambda: L.msf_debug_get(z, 0, 0, 0, z, 0, C.byref(C.c_size_t(0))),
         "msf_debug_loftr_head": lambda: L.msf_debug_loftr_head(z, 1, z, z, z, 16, z, z),
         "msf_debug_loftr_transformer": lambda: L.msf_debug_loftr_transformer(z, 1, 0, 8, z, z, z, z, z),
+        "msf_debug_loftr_backbone": lambda: L.msf_debug_loftr_backbone(z, 1, z, z, 0, 0, 0, z, z, z),
         "msf_set_mappoints": lambda: L.msf_set_mappoints(z, 0, z, 0),
         "msf_count_mappoint_matches_device": lambda: L.msf_count_mappoint_matches_device(z, 1, z, 16, z, z, z, z, z),
         "msf_store_frame": lambda: L.msf_store_frame(z, 0, None),
@@ -164,6 +165,7 @@ def test_bad_arguments_and_the_call_after(orb, loftr, frames):
     lo = torch.zeros((1, 4096, 4), dtype=torch.int32, device="cuda")
     ln = torch.zeros(1, dtype=torch.int32, device="cuda")
     f0, f1, g0, g1 = feat[0].data_ptr(), feat[1].data_ptr(), feat_o[0].data_ptr(), feat_o[1].data_ptr()
+    tok = torch.zeros((2, 2, 1200, 32), dtype=torch.float32, device="cuda")
     la, lb = synth.synth_pair(60, 640, 480, mode=1, shift=(32, 16))
     ld = _device_frames(np.stack([la, la]), np.stack([lb, lb]), 640)
     batch0 = _lib.RansacBatch(struct_size=0)
@@ -200,6 +202,7 @@ def test_bad_arguments_and_the_call_after(orb, loftr, frames):
                                                  loftr.match_slots_device(d_s0[:1], d_s1[:1], lo, ln)),
         "msf_debug_loftr_head": lambda: loftr.head_device(feat[0], feat[1], lo, ln),
         "msf_debug_loftr_transformer": lambda: loftr.transformer_device(feat[0], feat[1], feat_o[0], feat_o[1], 0, 2),
+        "msf_debug_loftr_backbone": lambda: loftr.backbone_device(ld[0], ld[1], tok[0], tok[1], act_image=3),
     }
     bad_arg = lambda e: e + ": bad argument"                                                     # noqa: E731
     # (handle, entry whose good call follows, what is wrong, call, status, text left in msf_last_error)
@@ -276,6 +279,9 @@ def test_bad_arguments_and_the_call_after(orb, loftr, frames):
          INV, "msf_debug_loftr_head: not a LoFTR handle"),
         (orb, "msf_debug_loftr_transformer", "ORB handle", lambda: L.msf_debug_loftr_transformer(h, 1, 0, 2, f0, f1, g0, g1, None),
          INV, "msf_debug_loftr_transformer: not a LoFTR handle"),
+        (orb, "msf_debug_loftr_backbone", "ORB handle",
+         lambda: L.msf_debug_loftr_backbone(h, 1, dA, dB, fs, PITCH, 0, tok[0].data_ptr(), tok[1].data_ptr(), None),
+         INV, "msf_debug_loftr_backbone: not a LoFTR handle"),
         (loftr, "loftr msf_match_batch_device", "n_pairs > max_batch_pairs",
          lambda: L.msf_match_batch_device(lh, P + 1, ld[0].data_ptr(), ld[1].data_ptr(), 640 * 480, 640, lo.data_ptr(), 64,
                                           ln.data_ptr(), None), INV, "n_pairs exceeds max_batch_pairs"),
@@ -292,13 +298,25 @@ def test_bad_arguments_and_the_call_after(orb, loftr, frames):
         (loftr, "msf_debug_loftr_transformer", "misaligned tokens",
          lambda: L.msf_debug_loftr_transformer(lh, 1, 0, 2, f0, f1, g0 + 8, g1, None),
          INV, "msf_debug_loftr_transformer: misaligned pointer"),
+        (loftr, "msf_debug_loftr_backbone", "act_image past the pass",
+         lambda: L.msf_debug_loftr_backbone(lh, 2, ld[0].data_ptr(), ld[1].data_ptr(), 640 * 480, 640, 4, tok[0].data_ptr(),
+                                            tok[1].data_ptr(), None), INV, bad_arg("msf_debug_loftr_backbone")),
+        (loftr, "msf_debug_loftr_backbone", "n above the backbone chunk",
+         lambda: L.msf_debug_loftr_backbone(lh, P + 1, ld[0].data_ptr(), None, 640 * 480, 640, 0, tok[0].data_ptr(), None, None),
+         INV, bad_arg("msf_debug_loftr_backbone")),
+        (loftr, "msf_debug_loftr_backbone", "misaligned frames",
+         lambda: L.msf_debug_loftr_backbone(lh, 1, ld[0].data_ptr() + 4, ld[1].data_ptr(), 640 * 480, 640, 0, tok[0].data_ptr(),
+                                            tok[1].data_ptr(), None), INV, "msf_debug_loftr_backbone: misaligned pointer"),
+        (loftr, "msf_debug_loftr_backbone", "row_stride < W",
+         lambda: L.msf_debug_loftr_backbone(lh, 1, ld[0].data_ptr(), ld[1].data_ptr(), 640 * 480, 624, 0, tok[0].data_ptr(),
+                                            tok[1].data_ptr(), None), INV, "row_stride < image_width"),
     ]
     for mt, entry, what, call, status, text in cases:
         label = "%s, %s" % (entry, what)
         before = _err(mt)
         assert call() == status, label
         assert _err(mt) == (before if text is None else text), label
-        if mt is loftr or not entry.startswith("msf_debug_loftr"):      # (an ORB handle has no good call of those two)
+        if mt is loftr or not entry.startswith("msf_debug_loftr"):      # (an ORB handle has no good call of those)
             good[entry]()
     # every entry with an argument check of its own has a refusal above whose text starts with the entry's name
     named = {e.split()[-1] for _, e, _, _, _, t in cases if t and t.startswith(e.split()[-1] + ":")}
