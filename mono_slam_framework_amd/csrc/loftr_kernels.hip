@@ -13,6 +13,10 @@
 // Activations in HBM: NCHW f32 (the graph's own layout: MFMA results store as float4 runs along W) everywhere except
 // BETWEEN the six streaming kernels of the default path, which hand each other "split pixels" -- channels-last 16-byte
 // pixels in [hi | lo] bf16 planes, the operand format of their LDS rings (see sx_off) -- so that the producer splits once.
+//
+// Weights: loftr_pack.h (host arithmetic, CPU-tested) defines every operand layout the kernels read -- the f32 matrices
+// of k_conv, the split-bf16 fragments of each convolution kernel, the encoder's slot orders -- and init() uploads them.
+#include "loftr_pack.h"
 #include "loftr_pipeline.h"
 #include "weights_io.h"
 
@@ -41,6 +45,8 @@
 #define MSF_LOFTR_DOWN16_DEPTH 3   // 110 registers, two workgroups per CU, no spills (4: 164 registers, one workgroup): 584 -> 475 us
 
 namespace msf {
+
+namespace pk = loftr_pack;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -524,6 +530,7 @@ constexpr int TP = 80;                             // t columns 64k-1 .. 64k+64 
 constexpr int TPLANE = TROWS * TP;
 constexpr int LDS_BYTES = 16 * (2 * XPLANE + 2 * TPLANE);   // 62 464: two workgroups per CU
 constexpr int WFRAG = 2 * 3 * 64 * 8;              // bf16 elements of one convolution's packed weights [hi|lo][kx][lane][8]
+static_assert(WFRAG == pk::frag_elems(pk::ConvFmt::Block8, 8), "k_block8x reads what loftr_pack.h writes");
 }  // namespace blk8x
 
 __device__ __forceinline__ void split_bf16(float v, __bf16& hi, __bf16& lo) {
@@ -1048,6 +1055,7 @@ constexpr int IDW = 37;                            // aligned dwords fetched per
 constexpr int NLOAD = 4 * IDW;                     // loader threads (4 image rows per step)
 constexpr int LDS_BYTES = 16 * (NS * 2 * RING + TAIL) + 2 * IROWS * IP + 64;
 constexpr int WFRAG = 2 * 3 * 64 * 8;              // stem fragments [hi | lo][row group][lane][8]
+static_assert(WFRAG == pk::frag_elems(pk::ConvFmt::Stem8, 1), "k_stem_strip8x reads what loftr_pack.h writes");
 }  // namespace stem8
 
 // r05: three workgroups per CU -- 51 KB of LDS (five-pair rings) and six waves per SIMD = 80 registers (86 uncapped: five
@@ -1286,6 +1294,8 @@ constexpr int NLOAD = 4 * INW;                     // loader threads: one input 
 constexpr int LDS_BYTES = 16 * (2 * IPLANE + 2 * TRING + 16);
 constexpr int W1FRAG = 2 * 3 * 64 * 8;             // conv3x3 stride 2: [hi | lo][ky][lane][8]
 constexpr int WSFRAG = 2 * 64 * 8;                 // shortcut: [hi | lo][lane][8]
+static_assert(W1FRAG == pk::frag_elems(pk::ConvFmt::Down16, 8) && WSFRAG == pk::frag_elems(pk::ConvFmt::Down16Sc, 8),
+              "k_down16x reads what loftr_pack.h writes");
 }  // namespace down16
 
 struct DownW {
@@ -2141,6 +2151,7 @@ static_assert(XCB % 16 == 0 && TCB % 16 == 0, "channel-block planes must be mult
 constexpr int G = 5;
 constexpr int LDS_BYTES = 16 * (4 * XCB + 4 * TCB);   // 73 728: two workgroups per CU
 constexpr int WFRAG = 2 * G * 64 * 8;              // bf16 elements of one convolution's fragments [hi | lo][g][lane][8]
+static_assert(WFRAG == pk::frag_elems(pk::ConvFmt::Block16, 16), "k_block16x reads what loftr_pack.h writes");
 }  // namespace blk16x
 
 __global__ __launch_bounds__(256, 2) void k_block16x(const float* __restrict__ in, const uint16_t* __restrict__ wx1,
@@ -2355,6 +2366,7 @@ struct Cfg {
   static constexpr int NITEMS = NCB * IN_H * IN_W;
   static constexpr int NLD = (NITEMS + 255) / 256;
 };
+static_assert(Cfg<32>::WSLOTS * 8 == pk::frag_elems(pk::ConvFmt::Convx, 32), "k_convx reads what loftr_pack.h writes");
 }  // namespace cvx
 
 template <int C, bool RES>
@@ -2501,6 +2513,8 @@ struct Cfg {
   static constexpr int XSLOTS = 2 * HLPLANE;
   static constexpr int WSLOTS = G * NT * 2 * 64;   // [g][cout tile][hi | lo][lane]
   static constexpr int SCSLOTS = NT * 2 * 64;      // shortcut: [cout tile][hi | lo][lane]
+  static_assert(WSLOTS * 8 == pk::frag_elems(pk::ConvFmt::Convx2, CIN) && SCSLOTS * 8 == pk::frag_elems(pk::ConvFmt::Convx2Sc, CIN),
+                "k_convx2 reads what loftr_pack.h writes");
   static constexpr int LDS_BYTES = 16 * (XSLOTS + WSLOTS);
   static constexpr int NITEMS = NCB * IN_H * IN_W;
   static constexpr int NLD = (NITEMS + 255) / 256;
@@ -2899,7 +2913,7 @@ __global__ __launch_bounds__(256) void k_out_tokens(const float* __restrict__ ac
 //   P8: operand rows that come from memory: slot (s, kq) <-> feature 8*kq + s, so a lane reads 8 contiguous floats;
 //   PD: operands that are MFMA results in registers (lane = column, regs = rows 4*(lane>>4)+r of each 16-row tile):
 //       slot (s', g) <-> feature 16*(s'/4) + 4*g + (s'%4), i.e. exactly the register the lane already holds.
-// Weights are re-ordered to those slot orders once on the host (pack_weight).
+// Weights are re-ordered to those slot orders once on the host (loftr_pack.h: pack_linear, pack_linear_split).
 struct BlockW {
   const float *wq_p, *wk_p, *wv_p, *wm_p, *w0_p, *w1_p;   // permuted: [(mtile*KS + slot)*64 + lane]
   const float *n1w, *n1b, *n2w, *n2b;
@@ -3498,6 +3512,7 @@ constexpr int kCandPerRow = 21;                       // >= 1 / (0.99 * kCandMin
 constexpr float kCandMinThreshold = 0.05f;            // below this the dense k_conf_mask pass is used
 constexpr int kCandCap = NTOK * kCandPerRow;          // per pair; cannot overflow for thresholds >= kCandMinThreshold
 struct SimCand { uint32_t ij; float s; };
+static_assert(sizeof(SimCand) == 8, "a candidate is two words");
 
 __global__ __launch_bounds__(256) void k_row_limits(const float* __restrict__ rstats, long long stats_stride,
                                                     float threshold, float* __restrict__ lim, int n_pairs,
@@ -4192,20 +4207,30 @@ __global__ __launch_bounds__(kDecThreads) void k_decode(const uint32_t* __restri
 }
 
 // ================================================================== host side
-struct ConvDesc {
+struct ConvDesc {       // the weight layouts are those of loftr_pack.h
   int cin, cout, ks, stride, hin, win, hout, wout;
-  float* d_w = nullptr;   // [KSTEPS*4][NPAD]
-  float* d_w2 = nullptr;  // row-packed variant (RP = 2) for the 8 -> 8 layers
-  uint16_t* d_wx = nullptr;  // split-bf16 fragments: 8 -> 8 layers (k_block8x) [hi | lo][kx][lane][8]; 32 -> 32 stride-1
-                             // layers (k_convx) [tap][cout tile][hi | lo][lane][8]
+  float* d_w = nullptr;   // pack_conv_f32
+  float* d_w2 = nullptr;  // pack_conv_rowpair (RP = 2), the 8-cout layers only
+  uint16_t* d_wx = nullptr;  // pack_conv_split: the fragments of the one split-bf16 kernel that runs this layer (conv_format)
   float* d_b = nullptr;   // [cout] or null
 };
 
 struct LoftrPipeline::Impl {
   int max_pairs = 0, chunk = 0;
   bool profile = false;
-  std::vector<float*> allocs;
-  ConvDesc conv[21];
+  std::vector<void*> allocs;   // everything dalloc() handed out: destroy() frees it
+  template <class T>
+  hipError_t dalloc(T** d, size_t count) {
+    hipError_t e = hipMalloc(d, count * sizeof(T));
+    if (e == hipSuccess) allocs.push_back(*d);
+    return e;
+  }
+  template <class T>
+  hipError_t upload(const std::vector<T>& h, T** d) {
+    hipError_t e = dalloc(d, h.size());
+    return e != hipSuccess ? e : hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+  }
+  ConvDesc conv[pk::kConvs];
   float* d_pe = nullptr;
   BlockW blk[8];
   // workspace (per chunk of pairs)
@@ -4282,7 +4307,7 @@ LoftrPipeline::~LoftrPipeline() { destroy(); }
 
 void LoftrPipeline::destroy() {
   if (!p_) return;
-  for (float* a : p_->allocs) hipFree(a);
+  for (void* a : p_->allocs) hipFree(a);
   for (auto& e : p_->ev) hipEventDestroy(e);
   delete p_;
   p_ = nullptr;
@@ -4345,273 +4370,48 @@ std::string LoftrPipeline::init(const char* weights_path, int max_pairs, bool pr
     if (it == blob.end() || it->second.data.size() != count) return nullptr;
     return &it->second.data;
   };
-  auto upload = [&](const std::vector<float>& h, float** d) -> hipError_t {
-    hipError_t e = hipMalloc(d, h.size() * sizeof(float));
-    if (e != hipSuccess) return e;
-    P.allocs.push_back(*d);
-    return hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
-  };
-  // backbone, index = execution order of the graph (and of the weight blob)
-  const int spec[21][6] = {
-      // cin cout ks stride hin win
-      {1, 8, 7, 2, 480, 640},   {8, 8, 3, 1, 240, 320},   {8, 8, 3, 1, 240, 320},   {8, 8, 3, 1, 240, 320},
-      {8, 8, 3, 1, 240, 320},   {8, 16, 3, 2, 240, 320},  {16, 16, 3, 1, 120, 160}, {8, 16, 1, 2, 240, 320},
-      {16, 16, 3, 1, 120, 160}, {16, 16, 3, 1, 120, 160}, {16, 32, 3, 2, 120, 160}, {32, 32, 3, 1, 60, 80},
-      {16, 32, 1, 2, 120, 160}, {32, 32, 3, 1, 60, 80},   {32, 32, 3, 1, 60, 80},   {32, 32, 3, 2, 60, 80},
-      {32, 32, 3, 1, 30, 40},   {32, 32, 1, 2, 60, 80},   {32, 32, 3, 1, 30, 40},   {32, 32, 3, 1, 30, 40},
-      {32, 32, 1, 1, 30, 40}};
-  for (int i = 0; i < 21; i++) {
+  for (int i = 0; i < pk::kConvs; i++) {
+    const pk::ConvShape& sh = pk::kConv[i];
     ConvDesc& c = P.conv[i];
-    c.cin = spec[i][0]; c.cout = spec[i][1]; c.ks = spec[i][2]; c.stride = spec[i][3]; c.hin = spec[i][4]; c.win = spec[i][5];
-    const int pad = c.ks / 2;
-    c.hout = (c.hin + 2 * pad - c.ks) / c.stride + 1;
-    c.wout = (c.win + 2 * pad - c.ks) / c.stride + 1;
+    c.cin = sh.cin; c.cout = sh.cout; c.ks = sh.ks; c.stride = sh.stride; c.hin = sh.hin; c.win = sh.win;
+    c.hout = sh.hout(); c.wout = sh.wout();
     char nm[32];
     if (i < 20) snprintf(nm, sizeof nm, "conv%02d.w", i); else snprintf(nm, sizeof nm, "outconv.w");
-    const auto* w = need(nm, (size_t)c.cout * c.cin * c.ks * c.ks);
+    const auto* w = need(nm, sh.weights());
     if (!w) return std::string("io: weights blob lacks ") + nm;
-    const int ktot = c.ks * c.ks * c.cin, ksteps = (ktot + 3) / 4, npad = ((c.cout + 15) / 16) * 16;
-    const int grp = ksteps >= 4 ? 4 : ksteps, ksteps_pad = ((ksteps + grp - 1) / grp) * grp;   // = ConvCfg::NG * G
-    std::vector<float> wb((size_t)ksteps_pad * 4 * npad, 0.f);
-    for (int co = 0; co < c.cout; co++)
-      for (int ci = 0; ci < c.cin; ci++)
-        for (int ky = 0; ky < c.ks; ky++)
-          for (int kx = 0; kx < c.ks; kx++) {
-            const int k = (ky * c.ks + kx) * c.cin + ci;
-            wb[(size_t)k * npad + co] = (*w)[(((size_t)co * c.cin + ci) * c.ks + ky) * c.ks + kx];
-          }
-    LF_TRY(upload(wb, &c.d_w));
-    if (c.cout == 8 && (c.stride == 1 || c.cin == 1)) {
-      // row-packed weights (RP = 2): k = ((kyy * ks + kx) * cin + ci) over ks + stride input rows,
-      // column = row_sel * 8 + co; output row rs sees input rows stride * rs .. stride * rs + ks - 1
-      const int kyy = c.ks + c.stride, kt2 = kyy * c.ks * c.cin, ks2 = (kt2 + 3) / 4;
-      const int g2 = ks2 >= 4 ? 4 : ks2, ks2_pad = ((ks2 + g2 - 1) / g2) * g2;   // = ConvCfg::NG * G
-      std::vector<float> w2((size_t)ks2_pad * 4 * 16, 0.f);
-      for (int rs = 0; rs < 2; rs++)
-        for (int co = 0; co < 8; co++)
-          for (int ci = 0; ci < c.cin; ci++)
-            for (int ky = 0; ky < c.ks; ky++)
-              for (int kx = 0; kx < c.ks; kx++) {
-                const int k = ((ky + c.stride * rs) * c.ks + kx) * c.cin + ci;
-                w2[(size_t)k * 16 + rs * 8 + co] = (*w)[(((size_t)co * c.cin + ci) * c.ks + ky) * c.ks + kx];
-              }
-      LF_TRY(upload(w2, &c.d_w2));
-    }
-    auto to_bf16 = [](float f) -> uint16_t {
-      uint32_t u;
-      memcpy(&u, &f, 4);
-      u += 0x7FFFu + ((u >> 16) & 1u);      // round to nearest even (weights are finite)
-      return (uint16_t)(u >> 16);
-    };
-    auto from_bf16 = [](uint16_t h) -> float {
-      const uint32_t u = (uint32_t)h << 16;
-      float f;
-      memcpy(&f, &u, 4);
-      return f;
-    };
-    auto upload16 = [&](const std::vector<uint16_t>& h, uint16_t** d) -> hipError_t {
-      hipError_t e = hipMalloc(reinterpret_cast<void**>(d), h.size() * sizeof(uint16_t));
-      if (e != hipSuccess) return e;
-      P.allocs.push_back(reinterpret_cast<float*>(*d));
-      return hipMemcpy(*d, h.data(), h.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-    };
-    if (c.cin == 1 && c.ks == 7) {
-      // k_stem_strip8x stage 0: fragment (hi | lo, row group g): element j = kx of lane (idx = co + 8 rs, kq) is
-      // w[co][ky = 4 g + kq - 2 rs][kx] / 255 (0 outside the 7 x 7 window); an output row pair spans image rows s = 0 .. 8
-      const float k255 = (float)(1.0 / 255.0);
-      std::vector<uint16_t> wx(stem8::WFRAG, 0);
-      for (int g = 0; g < 3; g++)
-        for (int l = 0; l < 64; l++)
-          for (int j = 0; j < 8; j++) {
-            const int co = l & 7, rs = (l >> 3) & 1, ky = 4 * g + (l >> 4) - 2 * rs;
-            const float v = (ky >= 0 && ky <= 6 && j <= 6) ? (*w)[((size_t)co * 7 + ky) * 7 + j] * k255 : 0.f;
-            const uint16_t hi = to_bf16(v), lo = to_bf16(v - from_bf16(hi));
-            wx[((size_t)(0 * 3 + g) * 64 + l) * 8 + j] = hi;
-            wx[((size_t)(1 * 3 + g) * 64 + l) * 8 + j] = lo;
-          }
-      LF_TRY(upload16(wx, &c.d_wx));
-    }
-    if (c.cout == 8 && c.cin == 8 && c.stride == 1) {
-      // k_block8x: element j of lane (idx = co + 8 rs, input row s) of fragment kx is w[co][ci = j][ky = s - rs][kx]
-      // (0 where output row rs does not see input row s), as hi = bf16(w) and lo = bf16(w - hi)
-      std::vector<uint16_t> wx(blk8x::WFRAG, 0);
-      for (int g = 0; g < 3; g++)
-        for (int l = 0; l < 64; l++)
-          for (int j = 0; j < 8; j++) {
-            const int co = l & 7, rs = (l >> 3) & 1, s = l >> 4, ky = s - rs;
-            const float v = (ky >= 0 && ky <= 2) ? (*w)[(((size_t)co * 8 + j) * 3 + ky) * 3 + g] : 0.f;
-            const uint16_t hi = to_bf16(v), lo = to_bf16(v - from_bf16(hi));
-            wx[((size_t)(0 * 3 + g) * 64 + l) * 8 + j] = hi;
-            wx[((size_t)(1 * 3 + g) * 64 + l) * 8 + j] = lo;
-          }
-      LF_TRY(upload16(wx, &c.d_wx));
-    }
-    if (c.cout == 16 && c.cin == 8 && c.stride == 2 && c.ks == 3) {
-      // k_down16x stage 1: fragment (hi | lo, ky): element j = ci of lane (cout l & 15, kx = l >> 4) is w[cout][ci][ky][kx]
-      // (kx = 3: zero)
-      std::vector<uint16_t> wx(down16::W1FRAG, 0);
-      for (int g = 0; g < 3; g++)
-        for (int l = 0; l < 64; l++)
-          for (int j = 0; j < 8; j++) {
-            const int co = l & 15, kx = l >> 4;
-            const float v = kx < 3 ? (*w)[(((size_t)co * 8 + j) * 3 + g) * 3 + kx] : 0.f;
-            const uint16_t hi = to_bf16(v), lo = to_bf16(v - from_bf16(hi));
-            wx[((size_t)(0 * 3 + g) * 64 + l) * 8 + j] = hi;
-            wx[((size_t)(1 * 3 + g) * 64 + l) * 8 + j] = lo;
-          }
-      LF_TRY(upload16(wx, &c.d_wx));
-    }
-    if (c.cout == 16 && c.cin == 8 && c.stride == 2 && c.ks == 1) {
-      // k_down16x shortcut: rides on the ky = 1 fragments, whose kx = 1 block is the pixel (2Y, 2X): other blocks zero
-      std::vector<uint16_t> wx(down16::WSFRAG, 0);
-      for (int l = 0; l < 64; l++)
-        for (int j = 0; j < 8; j++) {
-          const int co = l & 15, kx = l >> 4;
-          const float v = kx == 1 ? (*w)[(size_t)co * 8 + j] : 0.f;
-          const uint16_t hi = to_bf16(v), lo = to_bf16(v - from_bf16(hi));
-          wx[((size_t)0 * 64 + l) * 8 + j] = hi;
-          wx[((size_t)1 * 64 + l) * 8 + j] = lo;
-        }
-      LF_TRY(upload16(wx, &c.d_wx));
-    }
-    if (c.cout == 16 && c.cin == 16 && c.stride == 1) {
-      // k_block16x: fragment (hi | lo, g): element j of lane (cout l & 15, kq = l >> 4) is
-      // w[cout][ci = 8 (kq & 1) + j][tap 2 g + (kq >> 1)] (0 for the tenth tap)
-      std::vector<uint16_t> wx(blk16x::WFRAG, 0);
-      for (int g = 0; g < blk16x::G; g++)
-        for (int l = 0; l < 64; l++)
-          for (int j = 0; j < 8; j++) {
-            const int co = l & 15, q = l >> 4, t = 2 * g + (q >> 1), ci = 8 * (q & 1) + j;
-            const float v = t < 9 ? (*w)[(((size_t)co * 16 + ci) * 3 + t / 3) * 3 + t % 3] : 0.f;
-            const uint16_t hi = to_bf16(v), lo = to_bf16(v - from_bf16(hi));
-            wx[((size_t)(0 * blk16x::G + g) * 64 + l) * 8 + j] = hi;
-            wx[((size_t)(1 * blk16x::G + g) * 64 + l) * 8 + j] = lo;
-          }
-      LF_TRY(upload16(wx, &c.d_wx));
-    }
-    if (c.cout == 32 && c.stride == 2 && c.ks == 3) {
-      // k_convx2<CIN>: fragment (g, cout tile n, hi | lo): lane (cout 16 n + (l & 15), kq = l >> 4), element j:
-      //   CIN = 32: w[cout][ci = 8 kq + j][tap g];  CIN = 16: w[cout][ci = 8 (kq & 1) + j][tap 2 g + (kq >> 1)] (tenth tap: 0)
-      const int G = c.cin == 32 ? 9 : 5;
-      std::vector<uint16_t> wx((size_t)G * 2 * 2 * 64 * 8, 0);
-      for (int g = 0; g < G; g++)
-        for (int n = 0; n < 2; n++)
-          for (int l = 0; l < 64; l++)
-            for (int j = 0; j < 8; j++) {
-              const int co = 16 * n + (l & 15), q = l >> 4;
-              const int t = c.cin == 32 ? g : 2 * g + (q >> 1), ci = c.cin == 32 ? 8 * q + j : 8 * (q & 1) + j;
-              const float v = t < 9 ? (*w)[(((size_t)co * c.cin + ci) * 3 + t / 3) * 3 + t % 3] : 0.f;
-              const uint16_t hi = to_bf16(v), lo = to_bf16(v - from_bf16(hi));
-              wx[((size_t)((g * 2 + n) * 2 + 0) * 64 + l) * 8 + j] = hi;
-              wx[((size_t)((g * 2 + n) * 2 + 1) * 64 + l) * 8 + j] = lo;
-            }
-      LF_TRY(upload16(wx, &c.d_wx));
-    }
-    if (c.cout == 32 && c.stride == 2 && c.ks == 1) {
-      // k_convx2 shortcut: rides on the centre tap's fragment: CIN = 32: every K block (channel block kq);
-      // CIN = 16: the blocks of tap 4 = kq 0, 1 of group 2 (kq 2, 3 hold tap 5: zero)
-      std::vector<uint16_t> wx((size_t)2 * 2 * 64 * 8, 0);
-      for (int n = 0; n < 2; n++)
-        for (int l = 0; l < 64; l++)
-          for (int j = 0; j < 8; j++) {
-            const int co = 16 * n + (l & 15), q = l >> 4;
-            const bool live = c.cin == 32 || q < 2;
-            const int ci = c.cin == 32 ? 8 * q + j : 8 * (q & 1) + j;
-            const float v = live ? (*w)[(size_t)co * c.cin + ci] : 0.f;
-            const uint16_t hi = to_bf16(v), lo = to_bf16(v - from_bf16(hi));
-            wx[((size_t)(n * 2 + 0) * 64 + l) * 8 + j] = hi;
-            wx[((size_t)(n * 2 + 1) * 64 + l) * 8 + j] = lo;
-          }
-      LF_TRY(upload16(wx, &c.d_wx));
-    }
-    if (c.cout == 32 && c.cin == 32 && c.stride == 1 && c.ks == 3) {
-      // k_convx<32>: fragment (tap g, cout tile n, hi | lo): element j of lane (cout 16 n + (l & 15), channel block l >> 4)
-      // is w[cout][ci = 8 (l >> 4) + j][ky = g / 3][kx = g % 3]
-      using F = cvx::Cfg<32>;
-      std::vector<uint16_t> wx((size_t)F::WSLOTS * 8, 0);
-      for (int g = 0; g < F::G; g++)
-        for (int n = 0; n < F::NT; n++)
-          for (int l = 0; l < 64; l++)
-            for (int j = 0; j < 8; j++) {
-              const int co = 16 * n + (l & 15), ci = 8 * (l >> 4) + j;
-              const float v = (*w)[(((size_t)co * 32 + ci) * 3 + g / 3) * 3 + g % 3];
-              const uint16_t hi = to_bf16(v), lo = to_bf16(v - from_bf16(hi));
-              wx[((size_t)((g * F::NT + n) * 2 + 0) * 64 + l) * 8 + j] = hi;
-              wx[((size_t)((g * F::NT + n) * 2 + 1) * 64 + l) * 8 + j] = lo;
-            }
-      LF_TRY(upload16(wx, &c.d_wx));
-    }
+    LF_TRY(P.upload(pk::pack_conv_f32(sh, *w), &c.d_w));
+    if (pk::has_rowpair(sh)) LF_TRY(P.upload(pk::pack_conv_rowpair(sh, *w), &c.d_w2));
+    if (pk::conv_format(sh) != pk::ConvFmt::None) LF_TRY(P.upload(pk::pack_conv_split(sh, *w), &c.d_wx));
     if (i < 20) {
       snprintf(nm, sizeof nm, "conv%02d.b", i);
       const auto* b = need(nm, c.cout);
       if (!b) return std::string("io: weights blob lacks ") + nm;
-      LF_TRY(upload(*b, &c.d_b));
+      LF_TRY(P.upload(*b, &c.d_b));
     }
   }
   {
     const auto* pe = need("pe", (size_t)DM * NTOK);
     if (!pe) return "io: weights blob lacks pe";
-    LF_TRY(upload(*pe, &P.d_pe));
+    LF_TRY(P.upload(*pe, &P.d_pe));
   }
   for (int b = 0; b < 8; b++) {
     char nm[32];
-    // slot orders (see the kernel comments): 0 = P8 (feature 8*kq + s), 1 = PD (feature 16*(s/4) + 4*kq + s%4);
-    // `split`: wmlp0's 64 inputs are [x (P8, 8 slots) | merged message (PD, 8 slots)]
-    struct { const char* n; int in, out; int order; const float** dst; } items[] = {
-        {"wq", 32, 32, 0, &P.blk[b].wq_p}, {"wk", 32, 32, 0, &P.blk[b].wk_p}, {"wv", 32, 32, 0, &P.blk[b].wv_p},
-        {"wmerge", 32, 32, 1, &P.blk[b].wm_p}, {"wmlp0", 64, 64, 2, &P.blk[b].w0_p}, {"wmlp1", 64, 32, 1, &P.blk[b].w1_p}};
-    for (auto& it : items) {
-      snprintf(nm, sizeof nm, "blk%d.%s", b, it.n);
+    BlockW& B = P.blk[b];
+    const float** dst[pk::kLinears] = {&B.wq_p, &B.wk_p, &B.wv_p, &B.wm_p, &B.w0_p, &B.w1_p};   // in pk::kLinear's order
+    const uint16_t** xdst[pk::kLinears] = {&B.wq_x, nullptr, nullptr, &B.wm_x, &B.w0_x, &B.w1_x};
+    for (int k = 0; k < pk::kLinears; k++) {
+      const pk::LinearSpec& it = pk::kLinear[k];
+      snprintf(nm, sizeof nm, "blk%d.%s", b, it.name);
       const auto* w = need(nm, (size_t)it.in * it.out);
       if (!w) return std::string("io: weights blob lacks ") + nm;
-      const int slots = it.in / 4, mtiles = it.out / 16;
-      std::vector<float> pk((size_t)it.in * it.out);
-      for (int mt = 0; mt < mtiles; mt++)
-        for (int sl = 0; sl < slots; sl++)
-          for (int ln = 0; ln < 64; ln++) {
-            const int kq = ln >> 4;
-            int feat;
-            if (it.order == 0) feat = 8 * kq + sl;
-            else if (it.order == 1) feat = 16 * (sl >> 2) + 4 * kq + (sl & 3);
-            else feat = sl < 8 ? 8 * kq + sl : 32 + 16 * ((sl - 8) >> 2) + 4 * kq + ((sl - 8) & 3);
-            pk[((size_t)mt * slots + sl) * 64 + ln] = (*w)[(size_t)feat * it.out + 16 * mt + (ln & 15)];
-          }
+      const std::vector<float> pw = pk::pack_linear(*w, it.in, it.out, it.order);
       float* d = nullptr;
-      LF_TRY(upload(pk, &d));
-      *it.dst = d;
-      // split-bf16 fragments of the matrices k_attn_update_x multiplies by: element j of lane ln of (mtile, K group kg)
-      // is slot 8 kg + j of the f32 packing above
-      const uint16_t** xdst = !strcmp(it.n, "wq") ? &P.blk[b].wq_x : !strcmp(it.n, "wmerge") ? &P.blk[b].wm_x
-                              : !strcmp(it.n, "wmlp0") ? &P.blk[b].w0_x : !strcmp(it.n, "wmlp1") ? &P.blk[b].w1_x : nullptr;
-      if (xdst) {
-        auto to_bf16 = [](float f) -> uint16_t {
-          uint32_t u;
-          memcpy(&u, &f, 4);
-          u += 0x7FFFu + ((u >> 16) & 1u);
-          return (uint16_t)(u >> 16);
-        };
-        auto from_bf16 = [](uint16_t h) -> float {
-          const uint32_t u = (uint32_t)h << 16;
-          float f;
-          memcpy(&f, &u, 4);
-          return f;
-        };
-        const int kgs = slots / 8;
-        std::vector<uint16_t> fx((size_t)mtiles * kgs * 2 * 64 * 8);
-        for (int mt = 0; mt < mtiles; mt++)
-          for (int kg = 0; kg < kgs; kg++)
-            for (int ln = 0; ln < 64; ln++)
-              for (int j = 0; j < 8; j++) {
-                const float v = pk[((size_t)mt * slots + kg * 8 + j) * 64 + ln];
-                const uint16_t hi = to_bf16(v), lo = to_bf16(v - from_bf16(hi));
-                fx[((((size_t)mt * kgs + kg) * 2 + 0) * 64 + ln) * 8 + j] = hi;
-                fx[((((size_t)mt * kgs + kg) * 2 + 1) * 64 + ln) * 8 + j] = lo;
-              }
+      LF_TRY(P.upload(pw, &d));
+      *dst[k] = d;
+      if (it.split) {
         uint16_t* dx = nullptr;
-        LF_TRY(hipMalloc(reinterpret_cast<void**>(&dx), fx.size() * sizeof(uint16_t)));
-        P.allocs.push_back(reinterpret_cast<float*>(dx));
-        LF_TRY(hipMemcpy(dx, fx.data(), fx.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        *xdst = dx;
+        LF_TRY(P.upload(pk::pack_linear_split(pw, it.in, it.out), &dx));
+        *xdst[k] = dx;
       }
     }
     struct { const char* n; const float** dst; } lns[] = {
@@ -4621,65 +4421,40 @@ std::string LoftrPipeline::init(const char* weights_path, int max_pairs, bool pr
       const auto* w = need(nm, 32);
       if (!w) return std::string("io: weights blob lacks ") + nm;
       float* d = nullptr;
-      LF_TRY(upload(*w, &d));
+      LF_TRY(P.upload(*w, &d));
       *it.dst = d;
     }
   }
   // workspace
-  auto dalloc = [&](float** d, size_t floats) -> hipError_t {
-    hipError_t e = hipMalloc(d, floats * sizeof(float));
-    if (e == hipSuccess) P.allocs.push_back(*d);
-    return e;
-  };
   const size_t big = (size_t)P.chunk * 2 * 8 * 240 * 320;
-  LF_TRY(dalloc(&P.bufA, big));
-  LF_TRY(dalloc(&P.bufB, big));
-  LF_TRY(dalloc(&P.bufC, big));
-  LF_TRY(dalloc(&P.bufD, big / 2));
-  for (int i = 0; i < 4; i++) LF_TRY(dalloc(&P.tok[i], (size_t)max_pairs * NTOK * DM));
-  LF_TRY(dalloc(&P.tok_cache, (size_t)P.n_slots * NTOK * DM));
-  LF_TRY(dalloc(&P.fsc, (size_t)2 * max_pairs * NTOK * DM));
-  {
-    float* m = nullptr;
-    LF_TRY(dalloc(&m, (size_t)3 * max_pairs * NTOK * DM));   // 2 x 3 bf16 planes = 3 floats per feature
-    P.fsp = reinterpret_cast<__bf16*>(m);
-  }
-  LF_TRY(dalloc(&P.kv, (size_t)2 * max_pairs * (DM * DM + DM)));     // two halves: a launch may carry two encoder blocks
-  LF_TRY(dalloc(&P.rstats, (size_t)max_pairs * 2 * NTOK));
-  LF_TRY(dalloc(&P.cstats, (size_t)max_pairs * 2 * NTOK));
-  {
-    float* m = nullptr;
-    LF_TRY(dalloc(&m, (size_t)max_pairs * NTOK * MASK_WORDS));
-    P.mask = reinterpret_cast<uint32_t*>(m);
-    // the last 16-bit chunk of every row (bits 1200 .. 1215) is never written: keep it zero
-    LF_TRY(hipMemset(P.mask, 0, (size_t)max_pairs * NTOK * MASK_WORDS * sizeof(uint32_t)));
-  }
-  LF_TRY(dalloc(&P.lim, (size_t)max_pairs * NTOK));
-  LF_TRY(dalloc(&P.gbound, (size_t)max_pairs));
-  LF_TRY(dalloc(&P.cpart, (size_t)max_pairs * kSimParts * NTOK));
-  LF_TRY(dalloc(&P.rpart, (size_t)max_pairs * kSimColParts * NTOK));
-  {
-    float* m = nullptr;
-    LF_TRY(dalloc(&m, (size_t)max_pairs));
-    P.sim_redo = reinterpret_cast<uint32_t*>(m);
-    if (P.sim_skip) {
-      LF_TRY(dalloc(&m, (size_t)max_pairs * kSimItemsPerPair * kSimColTiles));
-      P.sim_tmax = reinterpret_cast<int*>(m);
-    }
-  }
-  {
-    float* m = nullptr;
-    LF_TRY(dalloc(&m, (size_t)max_pairs * kCandCap * 2));
-    P.cand = reinterpret_cast<SimCand*>(m);
-    LF_TRY(dalloc(&m, (size_t)max_pairs));
-    P.cand_cnt = reinterpret_cast<uint32_t*>(m);
-  }
-  LF_TRY(dalloc(&P.conf_dbg, (size_t)NTOK * NTOK));
-  LF_TRY(dalloc(&P.feat_dbg, (size_t)2 * NTOK * DM));
+  LF_TRY(P.dalloc(&P.bufA, big));
+  LF_TRY(P.dalloc(&P.bufB, big));
+  LF_TRY(P.dalloc(&P.bufC, big));
+  LF_TRY(P.dalloc(&P.bufD, big / 2));
+  for (int i = 0; i < 4; i++) LF_TRY(P.dalloc(&P.tok[i], (size_t)max_pairs * NTOK * DM));
+  LF_TRY(P.dalloc(&P.tok_cache, (size_t)P.n_slots * NTOK * DM));
+  LF_TRY(P.dalloc(&P.fsc, (size_t)2 * max_pairs * NTOK * DM));
+  LF_TRY(P.dalloc(&P.fsp, (size_t)2 * max_pairs * 3 * NTOK * DM));   // three bf16 planes per feature
+  LF_TRY(P.dalloc(&P.kv, (size_t)2 * max_pairs * (DM * DM + DM)));     // two halves: a launch may carry two encoder blocks
+  LF_TRY(P.dalloc(&P.rstats, (size_t)max_pairs * 2 * NTOK));
+  LF_TRY(P.dalloc(&P.cstats, (size_t)max_pairs * 2 * NTOK));
+  LF_TRY(P.dalloc(&P.mask, (size_t)max_pairs * NTOK * MASK_WORDS));
+  // the last 16-bit chunk of every row (bits 1200 .. 1215) is never written: keep it zero
+  LF_TRY(hipMemset(P.mask, 0, (size_t)max_pairs * NTOK * MASK_WORDS * sizeof(uint32_t)));
+  LF_TRY(P.dalloc(&P.lim, (size_t)max_pairs * NTOK));
+  LF_TRY(P.dalloc(&P.gbound, (size_t)max_pairs));
+  LF_TRY(P.dalloc(&P.cpart, (size_t)max_pairs * kSimParts * NTOK));
+  LF_TRY(P.dalloc(&P.rpart, (size_t)max_pairs * kSimColParts * NTOK));
+  LF_TRY(P.dalloc(&P.sim_redo, (size_t)max_pairs));
+  if (P.sim_skip) LF_TRY(P.dalloc(&P.sim_tmax, (size_t)max_pairs * kSimItemsPerPair * kSimColTiles));
+  LF_TRY(P.dalloc(&P.cand, (size_t)max_pairs * kCandCap));
+  LF_TRY(P.dalloc(&P.cand_cnt, (size_t)max_pairs));
+  LF_TRY(P.dalloc(&P.conf_dbg, (size_t)NTOK * NTOK));
+  LF_TRY(P.dalloc(&P.feat_dbg, (size_t)2 * NTOK * DM));
   if (keep_debug) {
     const size_t act_elems[4] = {8u * 240 * 320, 16u * 120 * 160, 32u * 60 * 80, 32u * 30 * 40};
-    for (int l = 0; l < 4; l++) LF_TRY(dalloc(&P.act_dbg[l], act_elems[l]));
-    LF_TRY(dalloc(&P.tok_dbg, (size_t)2 * NTOK * DM));
+    for (int l = 0; l < 4; l++) LF_TRY(P.dalloc(&P.act_dbg[l], act_elems[l]));
+    LF_TRY(P.dalloc(&P.tok_dbg, (size_t)2 * NTOK * DM));
   }
   if (profile) {
     P.ev.resize(4 * Impl::kEvRing);
