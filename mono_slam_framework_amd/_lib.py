@@ -1,4 +1,4 @@
-"""ctypes view of include/msf_abi.h, include/msf_initializer.h and include/msf_local_mapping.h.  Loading fails loudly when libmsf.so is missing: there is no CPU fallback."""
+"""ctypes view of include/msf_abi.h, include/msf_initializer.h, include/msf_local_mapping.h and include/msf_pnp.h.  Loading fails loudly when libmsf.so is missing: there is no CPU fallback."""
 import ctypes as C
 import os
 
@@ -49,6 +49,9 @@ INITIALIZER_SYMBOLS = ["msf_initializer_version", "msf_reconstruct", "msf_recons
 
 # every symbol include/msf_local_mapping.h declares (again a header and a version of its own)
 LOCAL_MAPPING_SYMBOLS = ["msf_local_mapping_version", "msf_new_points", "msf_new_points_device", "msf_create_map_points"]
+
+# every symbol include/msf_pnp.h declares (again a header and a version of its own)
+PNP_SYMBOLS = ["msf_pnp_version", "msf_pnp_ransac", "msf_pnp_ransac_device"]
 
 
 class Config(C.Structure):
@@ -103,6 +106,37 @@ class NewPointsResult(C.Structure):
     msf_new_points_device"""
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_new", C.c_void_p), ("packed", C.c_void_p),
                 ("status", C.c_void_p), ("points", C.c_void_p), ("hom", C.c_void_p), ("cos_parallax", C.c_void_p)]
+
+
+class PnpParams(C.Structure):
+    """msf_pnp_params: the current frame's intrinsics and SetRansacParameters' values after its adjustment"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("fx", C.c_float), ("fy", C.c_float),
+                ("cx", C.c_float), ("cy", C.c_float), ("th2", C.c_float), ("min_inliers", C.c_int32),
+                ("n_iterations", C.c_int32), ("max_records", C.c_int32), ("seed", C.c_uint64)]
+
+
+# msf_pnp_result's arrays in declaration order: name -> (dtype, per "hyp" / "rec" / "list", trailing shape; "cap" = the lists' stride)
+PNP_ARRAYS = [("n_records", "int32", "list", ()), ("counts", "int32", "hyp", ()),
+              ("iteration", "int32", "rec", ()), ("n_inliers", "int32", "rec", ()), ("refined_ok", "int32", "rec", ()),
+              ("n_refined", "int32", "rec", ()), ("Tcw_best", "float32", "rec", (12,)), ("Tcw_refined", "float32", "rec", (12,)),
+              ("inliers_best", "uint8", "rec", ("cap",)), ("inliers_refined", "uint8", "rec", ("cap",)),
+              ("sets", "int32", "hyp", (4,)), ("pose_f64", "float64", "hyp", (12,)), ("cws", "float64", "hyp", (4, 3)),
+              ("ut_tail", "float64", "hyp", (4, 12)), ("betas", "float64", "hyp", (3, 4)), ("rep_errors", "float64", "hyp", (3,)),
+              ("pca", "float64", "hyp", (3, 3)),
+              ("rec_pose_f64", "float64", "rec", (12,)), ("rec_cws", "float64", "rec", (4, 3)),
+              ("rec_ut_tail", "float64", "rec", (4, 12)), ("rec_betas", "float64", "rec", (3, 4)),
+              ("rec_rep_errors", "float64", "rec", (3,)), ("rec_pca", "float64", "rec", (3, 3))]
+
+
+class PnpResult(C.Structure):
+    """msf_pnp_result: host pointers for msf_pnp_ransac, device pointers for msf_pnp_ransac_device"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(a[0], C.c_void_p) for a in PNP_ARRAYS]
+
+
+def pnp_shapes(lists, n_iterations, max_records, cap):
+    """-> {name: (shape, dtype name)} of msf_pnp_result's arrays"""
+    lead = {"list": (lists,), "hyp": (lists, n_iterations), "rec": (lists, max_records)}
+    return {name: (lead[per] + tuple(cap if t == "cap" else t for t in tail), dt) for name, dt, per, tail in PNP_ARRAYS}
 
 
 VIEW_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4")])
@@ -162,6 +196,9 @@ def load():
                                         C.POINTER(NewPointsResult), vp]
     L.msf_create_map_points.argtypes = [vp, i32, vp, i32, vp, vp, C.POINTER(NewPointsParams), vp, vp, i32,
                                         C.POINTER(NewPointsResult)]
+    L.msf_pnp_version.restype = C.c_int
+    L.msf_pnp_ransac.argtypes = [vp, i32, vp, vp, C.POINTER(PnpParams), vp, C.POINTER(PnpResult)]
+    L.msf_pnp_ransac_device.argtypes = [vp, i32, vp, vp, i32, vp, C.POINTER(PnpParams), vp, C.POINTER(PnpResult), vp]
     L.msf_render_match_image.argtypes = [vp, C.POINTER(Image), C.POINTER(Image), vp, i32, vp, vp, vp, i64]
     L.msf_weights_info.argtypes = [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(i64)]
     L.msf_convert_weights.argtypes = [C.c_char_p, C.c_char_p]

@@ -1,0 +1,318 @@
+// hip_pnp_solver.h -- C++ host mirror of SLAM_PIPELINE::PnPsolver (slam_pipeline/include/PnPsolver.h,
+// slam_pipeline/src/PnPsolver.cc:69-331) above the C ABI: the surface Tracking::Relocalization (Tracking.cc:738-864)
+// uses -- the constructor, SetRansacParameters, iterate, find -- with every EPnP solve, inlier count and Refine done by
+// msf_pnp_ransac / msf_pnp_ransac_device (include/msf_pnp.h).
+//
+// The reference solves one hypothesis per loop turn on the CPU.  Here a solver keeps a cache of what the stateless
+// device call returned for iterations [0, cached): the inlier count of every iteration and the records (the iterations
+// at which mvbBestInliers is replaced) with their refined poses; iterate() replays :172-257 over that cache, the
+// count of iterations done and the best state included.  The loop runs while fewer than mRansacMaxIts iterations have
+// been done in total or fewer than nIterations in this call, as the reference's does, so the first call runs to
+// mRansacMaxIts.  When a call needs iterations beyond the
+// cache, the stateless call is issued again with a larger n_iterations: the sets are drawn here from (seed, key,
+// iteration), so the earlier iterations come out as they were.  Relocalization round-robins over the candidates'
+// solvers: PnPsolver::Prefetch fills all their caches with ONE msf_pnp_ransac_device call.
+//
+// Header-only and OpenCV-free, like hip_initializer.h: a 3-D point is three floats, a 2-D point two, Tcw a row-major
+// float[16], "no pose" (the reference's empty cv::Mat) a false return.  The gather of the 3-D points (:80-112:
+// GetMapPoint2(i), isBad(), GetWorldPos()) stays with the caller, who passes what the reference's constructor builds:
+// mvP3Dw, mvP2D, mvKeyPointIndices and the number of matches.  See INTEGRATION.md.
+#pragma once
+
+#ifndef __HIP_PLATFORM_AMD__
+#define __HIP_PLATFORM_AMD__ 1
+#endif
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "msf_pnp.h"
+#include "pnp_solve.h"   // draw_set4: the minimum sets are drawn here and handed to the call
+
+namespace msf {
+
+#ifndef MSF_POINT3F_DEFINED
+#define MSF_POINT3F_DEFINED
+struct Point3f {   // cv::Point3f
+  float x, y, z;
+};
+#endif
+
+#ifndef MSF_POINT2F_DEFINED
+#define MSF_POINT2F_DEFINED
+struct Point2f {   // cv::Point2f
+  float x, y;
+};
+#endif
+
+class PnPsolver {
+ public:
+  // What PnPsolver::PnPsolver(matchResult) leaves in mvP3Dw, mvP2D, mvKeyPointIndices; nMatches =
+  // matchResult.keyPoints2.size(); the intrinsics of the current frame.  `seed` and `key` name this solver's draws.
+  PnPsolver(msf_handle* handle, const std::vector<Point3f>& vP3Dw, const std::vector<Point2f>& vP2D,
+            const std::vector<size_t>& vKeyPointIndices, size_t nMatches, float fx, float fy, float cx, float cy,
+            uint64_t seed = 0, int32_t key = 0)
+      : h_(handle), p3d_(vP3Dw), p2d_(vP2D), idx_(vKeyPointIndices), n_matches_(nMatches), fx_(fx), fy_(fy), cx_(cx),
+        cy_(cy), seed_(seed), key_(key) {
+    SetRansacParameters();
+  }
+
+  // The adjustment of the reference's SetRansacParameters, in its types: the floor is the larger of minInliers, minSet
+  // and epsilon N truncated (a float product); epsilon is raised to floor / N (a float quotient); the iteration count is
+  // 1 when every correspondence has to be an inlier, else ceil(log(1 - probability) / log(1 - epsilon^3)) in double
+  // with epsilon promoted -- the cube, not the fourth power, although minSet is 4 -- clamped to [1, maxIterations].
+  void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4,
+                           float epsilon = 0.4f, float th2 = 5.991f) {
+    n_ = static_cast<int>(p2d_.size());
+    floor_ = std::max(std::max(static_cast<int>(n_ * epsilon), minInliers), minSet);
+    const float share = static_cast<float>(floor_) / n_;
+    const float eps = epsilon < share ? share : epsilon;
+    int wanted = 1;
+    if (floor_ != n_) {
+      const double miss = 1 - std::pow(static_cast<double>(eps), 3);
+      wanted = static_cast<int>(std::ceil(std::log(1 - probability) / std::log(miss)));
+    }
+    max_its_ = std::max(1, std::min(wanted, maxIterations));
+    th2_ = th2;
+    cached_ = 0;   // the floor and the threshold are part of what the cache holds
+  }
+
+  bool find(std::vector<bool>& vbInliers, int& nInliers, float Tcw[16]) {
+    bool ignored;
+    return iterate(max_its_, ignored, vbInliers, nInliers, Tcw);
+  }
+
+  // The reference's iterate over the cache.  It keeps going while fewer than max_its_ iterations have been done in
+  // total OR fewer than nIterations in this call (so the first call runs to max_its_).  An iteration below the floor
+  // changes nothing; one at or above it first replaces the best record if its count is strictly larger, then asks
+  // whether the CURRENT best record's refine succeeded (more refined inliers than the floor, strictly): if so that is
+  // the return.  When the loop ends, bNoMore is set and the best record, if there is one, is returned unrefined.
+  // true: Tcw holds a pose; false: the reference's empty matrix.
+  bool iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers, float Tcw[16]) {
+    bNoMore = false;
+    vbInliers.clear();
+    nInliers = 0;
+    if (n_ < floor_) {
+      bNoMore = true;
+      return false;
+    }
+    for (int here = 0; done_ < max_its_ || here < nIterations; here++) {
+      const int it = done_++;
+      if (it >= cached_ && !Fill(std::max(std::max(2 * cached_, it + 1), max_its_))) {
+        bNoMore = true;   // the device call failed: msf_last_error(handle) has the text
+        return false;
+      }
+      const int count = counts_[it];
+      if (count < floor_) continue;
+      if (count > best_count_) {
+        best_count_ = count;
+        best_ = RecordOf(it);
+      }
+      const Record& r = records_[best_];
+      if (r.n_refined > floor_) return Report(r.n_refined, r.inliers_refined, r.Tcw_refined, vbInliers, nInliers, Tcw);
+    }
+    bNoMore = done_ >= max_its_;
+    if (!bNoMore || best_count_ < floor_) return false;
+    const Record& r = records_[best_];
+    return Report(best_count_, r.inliers_best, r.Tcw_best, vbInliers, nInliers, Tcw);
+  }
+
+  // Fills the caches of all the solvers (the candidates of one Relocalization) for iterations [0, their largest
+  // max_its_) with one msf_pnp_ransac_device call on a block allocated here.  The calling thread's current HIP
+  // device must be the handle's.  false: a failed call, or solvers that do not share handle, intrinsics and th2 (nothing is
+  // filled then; each solver still fills its own cache when iterate needs it).
+  static bool Prefetch(const std::vector<PnPsolver*>& solvers) {
+    if (solvers.empty()) return true;
+    msf_handle* h = solvers[0]->h_;
+    for (const PnPsolver* s : solvers) {   // one call has one handle, one camera and one threshold
+      const PnPsolver* f = solvers[0];
+      if (!s || s->h_ != h || s->fx_ != f->fx_ || s->fy_ != f->fy_ || s->cx_ != f->cx_ || s->cy_ != f->cy_ ||
+          !(s->th2_ == f->th2_))
+        return false;
+    }
+    const size_t L = solvers.size();
+    int its = 1, floor = 0x7fffffff;
+    size_t cap = 1;
+    for (const PnPsolver* s : solvers) {
+      its = std::max(its, s->max_its_);
+      floor = std::min(floor, s->floor_);
+      cap = std::max(cap, s->p3d_.size());
+    }
+    const int max_records = kMaxRecords;
+    std::vector<float> p3(L * cap * 3, 0.0f), p2(L * cap * 2, 0.0f);
+    std::vector<int32_t> n(L), sets(L * its * 4, 0);
+    for (size_t l = 0; l < L; l++) {
+      const PnPsolver* s = solvers[l];
+      n[l] = static_cast<int32_t>(s->p3d_.size());
+      if (n[l]) std::memcpy(&p3[l * cap * 3], s->p3d_.data(), n[l] * sizeof(Point3f));
+      if (n[l]) std::memcpy(&p2[l * cap * 2], s->p2d_.data(), n[l] * sizeof(Point2f));
+      if (n[l] >= 4)
+        for (int it = 0; it < its; it++) pnp::draw_set4(s->seed_, s->key_, it, n[l], &sets[(l * its + it) * 4]);
+    }
+    // one block: inputs, then the outputs the cache keeps
+    const size_t recs = L * max_records;
+    const size_t sizes[] = {p3.size() * 4, p2.size() * 4, n.size() * 4, sets.size() * 4, L * 4, L * its * 4,
+                            recs * 4, recs * 4, recs * 4, recs * 48, recs * 48, recs * cap, recs * cap};
+    size_t off[14] = {0};
+    for (int k = 0; k < 13; k++) off[k + 1] = off[k] + ((sizes[k] + 255) & ~static_cast<size_t>(255));
+    char* base = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&base), off[13]) != hipSuccess) return false;
+    bool ok = hipMemcpy(base + off[0], p3.data(), sizes[0], hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(base + off[1], p2.data(), sizes[1], hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(base + off[2], n.data(), sizes[2], hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(base + off[3], sets.data(), sizes[3], hipMemcpyHostToDevice) == hipSuccess;
+    msf_pnp_params prm = solvers[0]->Params(its, max_records);
+    prm.min_inliers = floor;
+    msf_pnp_result out;
+    std::memset(&out, 0, sizeof out);
+    out.struct_size = sizeof out;
+    out.n_records = reinterpret_cast<int32_t*>(base + off[4]);
+    out.counts = reinterpret_cast<int32_t*>(base + off[5]);
+    out.iteration = reinterpret_cast<int32_t*>(base + off[6]);
+    out.n_inliers = reinterpret_cast<int32_t*>(base + off[7]);
+    out.n_refined = reinterpret_cast<int32_t*>(base + off[8]);
+    out.Tcw_best = reinterpret_cast<float*>(base + off[9]);
+    out.Tcw_refined = reinterpret_cast<float*>(base + off[10]);
+    out.inliers_best = reinterpret_cast<uint8_t*>(base + off[11]);
+    out.inliers_refined = reinterpret_cast<uint8_t*>(base + off[12]);
+    ok = ok && msf_pnp_ransac_device(h, static_cast<int32_t>(L), reinterpret_cast<const float*>(base + off[0]),
+                                     reinterpret_cast<const float*>(base + off[1]), static_cast<int32_t>(cap),
+                                     reinterpret_cast<const int32_t*>(base + off[2]), &prm,
+                                     reinterpret_cast<const int32_t*>(base + off[3]), &out, nullptr) == MSF_OK;
+    std::vector<int32_t> n_records(L), counts(L * its), iteration(recs), n_inliers(recs), n_refined(recs);
+    std::vector<float> tb(recs * 12), tr(recs * 12);
+    std::vector<uint8_t> ib(recs * cap), ir(recs * cap);
+    void* host[] = {n_records.data(), counts.data(), iteration.data(), n_inliers.data(), n_refined.data(),
+                    tb.data(),        tr.data(),     ib.data(),        ir.data()};
+    for (int k = 0; k < 9 && ok; k++)
+      ok = hipMemcpy(host[k], base + off[4 + k], sizes[4 + k], hipMemcpyDeviceToHost) == hipSuccess;
+    hipFree(base);
+    if (!ok) return false;
+    for (size_t l = 0; l < L; l++) {
+      PnPsolver* s = solvers[l];
+      if (n_records[l] < 0 || n_records[l] > max_records) continue;   // no list, or too many records: the solver asks itself
+      s->counts_.assign(counts.begin() + l * its, counts.begin() + (l + 1) * its);
+      s->sets_.assign(sets.begin() + l * its * 4, sets.begin() + (l + 1) * its * 4);
+      s->records_.clear();
+      for (int r = 0; r < n_records[l]; r++) {
+        const size_t at = l * max_records + r;
+        if (n_inliers[at] < s->floor_) continue;   // a record of the call's lower floor only
+        s->records_.push_back(Record{iteration[at], n_inliers[at], n_refined[at], {}, {}, {}, {}});
+        Record& rec = s->records_.back();
+        std::memcpy(rec.Tcw_best, &tb[at * 12], 48);
+        std::memcpy(rec.Tcw_refined, &tr[at * 12], 48);
+        rec.inliers_best.assign(ib.begin() + at * cap, ib.begin() + at * cap + n[l]);
+        rec.inliers_refined.assign(ir.begin() + at * cap, ir.begin() + at * cap + n[l]);
+      }
+      s->cached_ = its;
+    }
+    return true;
+  }
+
+  int minInliers() const { return floor_; }
+  int maxIterations() const { return max_its_; }
+  int iterations() const { return done_; }
+  int cached() const { return cached_; }
+  const std::vector<int32_t>& sets() const { return sets_; }       // [cached][4]
+  const std::vector<int32_t>& counts() const { return counts_; }   // [cached]
+
+ private:
+  static constexpr int kMaxRecords = 16;
+
+  struct Record {
+    int32_t iteration, n_inliers, n_refined;
+    float Tcw_best[12], Tcw_refined[12];
+    std::vector<uint8_t> inliers_best, inliers_refined;
+  };
+
+  msf_pnp_params Params(int its, int max_records) const {
+    msf_pnp_params prm;
+    std::memset(&prm, 0, sizeof prm);
+    prm.struct_size = sizeof prm;
+    prm.fx = fx_, prm.fy = fy_, prm.cx = cx_, prm.cy = cy_;
+    prm.th2 = th2_;
+    prm.min_inliers = floor_;
+    prm.n_iterations = its;
+    prm.max_records = max_records;
+    prm.seed = seed_;
+    return prm;
+  }
+
+  // the stateless call for iterations [0, its) of this solver alone
+  bool Fill(int its) {
+    if (!h_ || n_ < 4 || its >= (1 << 20)) return false;
+    std::vector<int32_t> sets(static_cast<size_t>(its) * 4);
+    for (int it = 0; it < its; it++) pnp::draw_set4(seed_, key_, it, n_, &sets[it * 4]);
+    for (int max_records = kMaxRecords;; max_records *= 2) {
+      std::vector<int32_t> counts(its), iteration(max_records), n_inliers(max_records), n_refined(max_records);
+      std::vector<float> tb(max_records * 12), tr(max_records * 12);
+      std::vector<uint8_t> ib(static_cast<size_t>(max_records) * n_), ir(static_cast<size_t>(max_records) * n_);
+      int32_t n_records = 0;
+      const msf_pnp_params prm = Params(its, max_records);
+      msf_pnp_result out;
+      std::memset(&out, 0, sizeof out);
+      out.struct_size = sizeof out;
+      out.n_records = &n_records, out.counts = counts.data(), out.iteration = iteration.data();
+      out.n_inliers = n_inliers.data(), out.n_refined = n_refined.data(), out.Tcw_best = tb.data();
+      out.Tcw_refined = tr.data(), out.inliers_best = ib.data(), out.inliers_refined = ir.data();
+      const int rc = msf_pnp_ransac(h_, n_, &p3d_[0].x, &p2d_[0].x, &prm, sets.data(), &out);
+      if (rc == MSF_ERR_CAPACITY && max_records < (1 << 16)) continue;
+      if (rc != MSF_OK) return false;
+      records_.clear();
+      for (int r = 0; r < n_records; r++) {
+        records_.push_back(Record{iteration[r], n_inliers[r], n_refined[r], {}, {}, {}, {}});
+        Record& rec = records_.back();
+        std::memcpy(rec.Tcw_best, &tb[r * 12], 48);
+        std::memcpy(rec.Tcw_refined, &tr[r * 12], 48);
+        rec.inliers_best.assign(ib.begin() + static_cast<size_t>(r) * n_, ib.begin() + static_cast<size_t>(r + 1) * n_);
+        rec.inliers_refined.assign(ir.begin() + static_cast<size_t>(r) * n_, ir.begin() + static_cast<size_t>(r + 1) * n_);
+      }
+      counts_.swap(counts);
+      sets_.swap(sets);
+      cached_ = its;
+      return true;
+    }
+  }
+
+  size_t RecordOf(int it) const {
+    for (size_t r = 0; r < records_.size(); r++)
+      if (records_[r].iteration == it) return r;
+    return 0;   // not reached: every iteration that raises the best count is a record
+  }
+
+  // the inlier flags scattered through mvKeyPointIndices over all matches, and rows 0..2 of Tcw completed to 4 x 4
+  bool Report(int count, const std::vector<uint8_t>& flags, const float* rt, std::vector<bool>& vbInliers, int& nInliers,
+              float Tcw[16]) const {
+    nInliers = count;
+    vbInliers.assign(n_matches_, false);
+    for (int i = 0; i < n_; i++)
+      if (flags[i]) vbInliers[idx_[i]] = true;
+    std::memcpy(Tcw, rt, 48);
+    Tcw[12] = Tcw[13] = Tcw[14] = 0.0f;
+    Tcw[15] = 1.0f;
+    return true;
+  }
+
+  msf_handle* h_;
+  std::vector<Point3f> p3d_;
+  std::vector<Point2f> p2d_;
+  std::vector<size_t> idx_;
+  size_t n_matches_;
+  float fx_, fy_, cx_, cy_, th2_ = 5.991f;
+  uint64_t seed_;
+  int32_t key_;
+  // what SetRansacParameters works out, and how far iterate has come
+  int n_ = 0, floor_ = 8, max_its_ = 300;
+  int done_ = 0, best_count_ = 0;
+  // the cache
+  int cached_ = 0;
+  size_t best_ = 0;
+  std::vector<int32_t> counts_, sets_;
+  std::vector<Record> records_;
+};
+
+}  // namespace msf

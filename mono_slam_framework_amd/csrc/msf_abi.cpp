@@ -15,7 +15,9 @@
 #include "loftr_pipeline.h"
 #include "msf_initializer.h"
 #include "msf_local_mapping.h"
+#include "msf_pnp.h"
 #include "orb_pipeline.h"
+#include "pnp_pipeline.h"
 #include "ransac_solve.h"
 #include "reconstruct_pipeline.h"
 #include "triangulate_pipeline.h"
@@ -104,6 +106,9 @@ struct msf_handle {
   // msf_new_points / msf_create_map_points workspace: the views, the results and the host call's list.  The first
   // msf_create_map_points sizes it for max_batch_pairs lists of stage_cap matches; a longer msf_new_points list grows it.
   DevBuf<uint8_t> d_lm;
+  // msf_pnp_ransac / msf_pnp_ransac_device workspace: the host call's list, sets and results; for the device call the
+  // counts and poses that the second launch reads when the caller does not ask for them
+  DevBuf<uint8_t> d_pnp;
   std::vector<msf_view> view_stage;   // [2][n]: the query's view once per pair, then the neighbours'
   // msf_render_match_image workspace: the RGB image (allocated once) and the match list + flags (grown on demand)
   DevBuf<uint8_t> d_render;      // [H][2 * W][3]
@@ -1278,6 +1283,165 @@ int msf_create_map_points(msf_handle* h, int32_t query_slot, const msf_view* que
     drain.armed = false;
     if (int rc = cs.finish()) return rc;
     return capacity ? fail(h, MSF_ERR_CAPACITY, kNoResult) : MSF_OK;
+  });
+}
+
+namespace {
+
+// Where an msf_pnp.h call keeps its device data.  `given`: the caller's device arrays (msf_pnp_ransac_device), kept
+// where they are; null: everything is carved (msf_pnp_ransac) and copied back.
+struct PnpPlan {
+  msf::PnpOut out{};
+  float* p3d = nullptr;
+  float* p2d = nullptr;
+  int32_t* sets_in = nullptr;
+};
+
+int plan_pnp(msf_handle* h, size_t lists, size_t cap, const msf_pnp_params* prm, const msf_pnp_result* given,
+             bool with_sets, PnpPlan* p) {
+  const size_t hyps = lists * (size_t)prm->n_iterations, recs = lists * (size_t)prm->max_records;
+  return carve(h, h->d_pnp, (size_t)1 << 16, "hipMalloc(pnp workspace)", [&](msf::Carver& c) {
+    msf::PnpOut& o = p->out;
+    if (given) {
+      o = msf::PnpOut{given->n_records, given->counts, given->iteration, given->n_inliers, given->refined_ok,
+                      given->n_refined, given->Tcw_best, given->Tcw_refined, given->inliers_best, given->inliers_refined,
+                      given->sets, given->pose_f64, given->cws, given->ut_tail, given->betas, given->rep_errors, given->pca,
+                      given->rec_pose_f64, given->rec_cws, given->rec_ut_tail, given->rec_betas, given->rec_rep_errors,
+                      given->rec_pca};
+      o.counts = c.take(o.counts, hyps);
+      o.pose_f64 = c.take(o.pose_f64, hyps * 12);
+      return;
+    }
+    p->p3d = c.take<float>(cap * 3);
+    p->p2d = c.take<float>(cap * 2);
+    p->sets_in = with_sets ? c.take<int32_t>(hyps * 4) : nullptr;
+    o.n_records = c.take<int32_t>(lists);
+    o.counts = c.take<int32_t>(hyps);
+    o.iteration = c.take<int32_t>(recs);
+    o.n_inliers = c.take<int32_t>(recs);
+    o.refined_ok = c.take<int32_t>(recs);
+    o.n_refined = c.take<int32_t>(recs);
+    o.tcw_best = c.take<float>(recs * 12);
+    o.tcw_refined = c.take<float>(recs * 12);
+    o.inliers_best = c.take<uint8_t>(recs * cap);
+    o.inliers_refined = c.take<uint8_t>(recs * cap);
+    o.sets = c.take<int32_t>(hyps * 4);
+    o.pose_f64 = c.take<double>(hyps * 12);
+    o.cws = c.take<double>(hyps * 12);
+    o.ut_tail = c.take<double>(hyps * 48);
+    o.betas = c.take<double>(hyps * 12);
+    o.rep_errors = c.take<double>(hyps * 3);
+    o.pca = c.take<double>(hyps * 9);
+    o.rec_pose_f64 = c.take<double>(recs * 12);
+    o.rec_cws = c.take<double>(recs * 12);
+    o.rec_ut_tail = c.take<double>(recs * 48);
+    o.rec_betas = c.take<double>(recs * 12);
+    o.rec_rep_errors = c.take<double>(recs * 3);
+    o.rec_pca = c.take<double>(recs * 9);
+  });
+}
+
+// nullptr when params and out are usable, else what is wrong with them
+const char* pnp_fault(const msf_pnp_params* prm, const msf_pnp_result* out) {
+  if (!out || out->struct_size != sizeof(msf_pnp_result)) return "out is NULL or out->struct_size is not sizeof(msf_pnp_result)";
+  if (!prm || prm->struct_size != sizeof(msf_pnp_params)) return "params is NULL or params->struct_size is not sizeof(msf_pnp_params)";
+  if (std::isnan(prm->th2)) return "th2 must not be NaN";
+  if (prm->min_inliers < 1) return "min_inliers < 1";
+  if (prm->n_iterations < 1 || prm->n_iterations >= (1 << 20)) return "n_iterations outside [1, 2^20)";
+  if (prm->max_records < 1) return "max_records < 1";
+  if (!out->n_records) return "a required pointer is NULL (out->n_records)";
+  return nullptr;
+}
+
+msf::PnpParams pnp_params(const msf_pnp_params* prm) {
+  return msf::PnpParams{prm->fx, prm->fy, prm->cx, prm->cy, prm->th2, prm->min_inliers, prm->n_iterations,
+                        prm->max_records, prm->seed};
+}
+
+}  // namespace
+
+int msf_pnp_version(void) { return MSF_PNP_VERSION; }
+
+int msf_pnp_ransac(msf_handle* h, int32_t n, const float* p3d, const float* p2d, const msf_pnp_params* params,
+                   const int32_t* sets, msf_pnp_result* out) {
+  return guarded(h, "msf_pnp_ransac", [&]() -> int {
+    if (const char* fault = pnp_fault(params, out)) return fail(h, MSF_ERR_INVALID_ARG, std::string("msf_pnp_ransac: ") + fault);
+    if (n < 0) return fail(h, MSF_ERR_INVALID_ARG, "msf_pnp_ransac: n is negative");
+    if (n > 0 && (!p3d || !p2d)) return fail(h, MSF_ERR_INVALID_ARG, "msf_pnp_ransac: a required pointer is NULL (p3d, p2d)");
+    CallScope cs{h};
+    if (int rc = cs.enter()) return rc;
+    const size_t cap = n > 0 ? (size_t)n : 1, its = (size_t)params->n_iterations;
+    PnpPlan p;
+    if (int rc = plan_pnp(h, 1, cap, params, nullptr, sets != nullptr, &p)) return rc;
+    hipStream_t st = cs.st;
+    Drain drain{st};
+    if (n > 0) {
+      HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.p3d, p3d, (size_t)n * 12, hipMemcpyHostToDevice, st));
+      HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.p2d, p2d, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    }
+    if (sets) HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.sets_in, sets, its * 16, hipMemcpyHostToDevice, st));
+    const msf::PnpLists in{p.p3d, p.p2d, (int32_t)cap, nullptr, n, p.sets_in};
+    HIP_TRY(h, "pnp_ransac", msf::pnp_ransac(1, in, pnp_params(params), p.out, st));
+    if (int rc = fetch(h, st, out->n_records, p.out.n_records, 4)) return rc;
+    HIP_TRY(h, "hipStreamSynchronize", hipStreamSynchronize(st));   // the count decides what else there is to copy
+    const int32_t records = out->n_records[0];
+    if (records >= 0) {
+      const msf::PnpOut& d = p.out;
+      if (int rc = fetch(h, st, out->counts, d.counts, its * 4)) return rc;
+      if (!sets)
+        if (int rc = fetch(h, st, out->sets, d.sets, its * 16)) return rc;
+      if (int rc = fetch(h, st, out->pose_f64, d.pose_f64, its * 96)) return rc;
+      if (int rc = fetch(h, st, out->cws, d.cws, its * 96)) return rc;
+      if (int rc = fetch(h, st, out->ut_tail, d.ut_tail, its * 384)) return rc;
+      if (int rc = fetch(h, st, out->betas, d.betas, its * 96)) return rc;
+      if (int rc = fetch(h, st, out->rep_errors, d.rep_errors, its * 24)) return rc;
+      if (int rc = fetch(h, st, out->pca, d.pca, its * 72)) return rc;
+      const size_t k = (size_t)(records < params->max_records ? records : params->max_records);
+      if (int rc = fetch(h, st, out->iteration, d.iteration, k * 4)) return rc;
+      if (int rc = fetch(h, st, out->n_inliers, d.n_inliers, k * 4)) return rc;
+      if (int rc = fetch(h, st, out->refined_ok, d.refined_ok, k * 4)) return rc;
+      if (int rc = fetch(h, st, out->n_refined, d.n_refined, k * 4)) return rc;
+      if (int rc = fetch(h, st, out->Tcw_best, d.tcw_best, k * 48)) return rc;
+      if (int rc = fetch(h, st, out->Tcw_refined, d.tcw_refined, k * 48)) return rc;
+      if (int rc = fetch(h, st, out->rec_pose_f64, d.rec_pose_f64, k * 96)) return rc;
+      if (int rc = fetch(h, st, out->rec_cws, d.rec_cws, k * 96)) return rc;
+      if (int rc = fetch(h, st, out->rec_ut_tail, d.rec_ut_tail, k * 384)) return rc;
+      if (int rc = fetch(h, st, out->rec_betas, d.rec_betas, k * 96)) return rc;
+      if (int rc = fetch(h, st, out->rec_rep_errors, d.rec_rep_errors, k * 24)) return rc;
+      if (int rc = fetch(h, st, out->rec_pca, d.rec_pca, k * 72)) return rc;
+      for (size_t rec = 0; rec < k; rec++) {   // a row ends with the list
+        if (int rc = fetch(h, st, from(out->inliers_best, rec * cap), d.inliers_best + rec * cap, (size_t)n)) return rc;
+        if (int rc = fetch(h, st, from(out->inliers_refined, rec * cap), d.inliers_refined + rec * cap, (size_t)n)) return rc;
+      }
+    }
+    drain.armed = false;
+    if (int rc = cs.finish()) return rc;
+    if (records > params->max_records)
+      return fail(h, MSF_ERR_CAPACITY, "msf_pnp_ransac: the list has more records than max_records; the first max_records are complete");
+    return MSF_OK;
+  });
+}
+
+int msf_pnp_ransac_device(msf_handle* h, int32_t n_lists, const float* d_p3d, const float* d_p2d, int32_t cap,
+                          const int32_t* d_n, const msf_pnp_params* params, const int32_t* d_sets, msf_pnp_result* out,
+                          void* stream) {
+  return guarded(h, "msf_pnp_ransac_device", [&]() -> int {
+    if (const char* fault = pnp_fault(params, out))
+      return fail(h, MSF_ERR_INVALID_ARG, std::string("msf_pnp_ransac_device: ") + fault);
+    if (n_lists < 0 || n_lists > 65535) return fail(h, MSF_ERR_INVALID_ARG, "msf_pnp_ransac_device: n_lists outside [0, 65535]");
+    if (cap < 1) return fail(h, MSF_ERR_INVALID_ARG, "msf_pnp_ransac_device: cap < 1");
+    if ((long long)n_lists * params->n_iterations > (1ll << 32))   // four hypotheses per workgroup, 2^31 - 1 workgroups
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_pnp_ransac_device: n_lists * n_iterations above 2^32");
+    if (n_lists > 0 && (!d_p3d || !d_p2d || !d_n))
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_pnp_ransac_device: a required pointer is NULL (d_p3d, d_p2d, d_n)");
+    if (n_lists == 0) return MSF_OK;
+    CallScope cs{h};
+    if (int rc = cs.enter(stream)) return rc;
+    PnpPlan p;
+    if (int rc = plan_pnp(h, (size_t)n_lists, (size_t)cap, params, out, false, &p)) return rc;
+    const msf::PnpLists in{d_p3d, d_p2d, cap, d_n, 0, d_sets};
+    HIP_TRY(h, "pnp_ransac", msf::pnp_ransac(n_lists, in, pnp_params(params), p.out, cs.st));
+    return cs.finish();
   });
 }
 

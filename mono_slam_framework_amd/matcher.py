@@ -393,6 +393,74 @@ class _Matcher:
             new.append(e)
         return num, out_lists, new
 
+    @staticmethod
+    def _pnp_params(K, th2, min_inliers, n_iterations, max_records, seed):
+        fx, fy, cx, cy = K
+        return _lib.PnpParams(struct_size=C.sizeof(_lib.PnpParams), fx=fx, fy=fy, cx=cx, cy=cy, th2=th2,
+                              min_inliers=min_inliers, n_iterations=n_iterations, max_records=max_records, seed=seed)
+
+    def pnp_ransac(self, p3d, p2d, K, min_inliers, n_iterations, th2=5.991, max_records=8, seed=0, sets=None):
+        """PnPsolver's RANSAC iterations [0, n_iterations) and Refine on one list (PnPsolver.cc:172-331): p3d f32 [n, 3]
+        (mvP3Dw), p2d f32 [n, 2] (mvP2D), K = (fx, fy, cx, cy), min_inliers = mRansacMinInliers after
+        SetRansacParameters' adjustment, sets int32 [n_iterations, 4] or None to draw them from `seed`.
+        -> dict: n_records (the true number; -1: fewer than 4 correspondences), capacity (True: more records than
+        max_records, the first max_records are complete), counts [n_iterations], the per-record arrays cut to the
+        records kept (iteration, n_inliers, refined_ok, n_refined, Tcw_best [., 12], Tcw_refined, inliers_best [., n],
+        inliers_refined, rec_*), and the per-hypothesis diagnostics sets, pose_f64, cws, ut_tail, betas, rep_errors, pca."""
+        p3 = np.ascontiguousarray(p3d, np.float32).reshape(-1, 3)
+        p2 = np.ascontiguousarray(p2d, np.float32).reshape(-1, 2)
+        n = len(p3)
+        assert len(p2) == n
+        shapes = _lib.pnp_shapes(1, n_iterations, max_records, max(n, 1))
+        d = {k: np.zeros(shape, dt) for k, (shape, dt) in shapes.items()}
+        s = None
+        if sets is not None:
+            s = np.ascontiguousarray(sets, np.int32).reshape(n_iterations, 4)
+            d["sets"][0] = s
+        res = _fill(_lib.PnpResult(), d)
+        prm = self._pnp_params(K, th2, min_inliers, n_iterations, max_records, seed)
+        rc = self._L.msf_pnp_ransac(self._h, n, p3.ctypes.data, p2.ctypes.data, C.byref(prm),
+                                    s.ctypes.data if s is not None else None, C.byref(res))
+        if rc != _lib.MSF_ERR_CAPACITY:
+            self._check(rc)
+        records = int(d["n_records"][0])
+        kept = min(max(records, 0), max_records)
+        out = dict(n_records=records, capacity=rc == _lib.MSF_ERR_CAPACITY)
+        for name, _, per, _ in _lib.PNP_ARRAYS[1:]:
+            out[name] = d[name][0, :kept] if per == "rec" else d[name][0]
+        out["inliers_best"], out["inliers_refined"] = out["inliers_best"][:, :n], out["inliers_refined"][:, :n]
+        return out
+
+    def pnp_ransac_device(self, d_p3d, d_p2d, d_n, K, min_inliers, n_iterations, th2=5.991, max_records=8, seed=0,
+                          d_sets=None, out=None, diagnostics=True, stream=None):
+        """The same for a batch in device memory: d_p3d f32 [L, cap, 3], d_p2d f32 [L, cap, 2], d_n int32 [L] (negative:
+        no valid list), d_sets int32 [L, n_iterations, 4] or None.  -> dict of CUDA tensors with a leading L, named and
+        shaped as msf_pnp_result says (per-record arrays [L, max_records, ...], inlier rows [.., cap]); without
+        `diagnostics` only n_records, counts and the per-record results.  `out`: tensors to write into instead of fresh
+        zeros.  Two launches, asynchronous on `stream` (None = handle stream + sync)."""
+        import torch
+        assert d_p3d.is_cuda and d_p2d.is_cuda and d_n.is_cuda and d_p3d.is_contiguous() and d_p2d.is_contiguous()
+        assert d_p3d.dtype == torch.float32 and d_p2d.dtype == torch.float32 and d_n.dtype == torch.int32
+        L, cap = d_p3d.shape[0], d_p3d.shape[1]
+        assert tuple(d_p3d.shape) == (L, cap, 3) and tuple(d_p2d.shape) == (L, cap, 2) and d_n.numel() == L
+        d = out
+        if d is None:
+            z = _zeros_on(d_p3d.device)
+            d = {k: z(shape, dt) for k, (shape, dt) in _lib.pnp_shapes(L, n_iterations, max_records, cap).items()}
+            if not diagnostics:
+                for name, _, per, _ in _lib.PNP_ARRAYS:
+                    if name.startswith("rec_") or (per == "hyp" and name != "counts"):
+                        del d[name]
+        if d_sets is not None:
+            assert d_sets.is_cuda and d_sets.is_contiguous() and d_sets.dtype == torch.int32
+            assert d_sets.numel() == L * n_iterations * 4
+        res = _fill(_lib.PnpResult(), d)
+        prm = self._pnp_params(K, th2, min_inliers, n_iterations, max_records, seed)
+        self._check(self._L.msf_pnp_ransac_device(self._h, L, d_p3d.data_ptr(), d_p2d.data_ptr(), cap, d_n.data_ptr(),
+                                                  C.byref(prm), d_sets.data_ptr() if d_sets is not None else None,
+                                                  C.byref(res), stream))
+        return d
+
     def render_match_image(self, frame1, frame2, matches, has_mp1=None, has_mp2=None):
         """Tracking::CreateCurrentMatchImage (Tracking.cc:899-940) -> uint8 [H, 2W, 3]."""
         a, b = self._image(frame1), self._image(frame2)
