@@ -12,7 +12,8 @@
  *
  * What stays with the caller: the gather of the 3-D points (GetMapPoint2(i), isBad(), GetWorldPos(), :80-112), the
  * adjustment of SetRansacParameters (:130-165, host arithmetic: csrc/hip_pnp_solver.h) and the iterate() bookkeeping
- * over the counts and records this call returns; Optimizer::PoseOptimization.
+ * over the counts and records this call returns.  (Optimizer::PoseOptimization, which Relocalization runs on this
+ * call's Tcw_refined and inliers_refined: include/msf_pose.h.)
  *
  * The call is stateless: it evaluates iterations [0, n_iterations) of every list.  A RECORD is an iteration whose
  * inlier count is at least min_inliers and strictly above every earlier count of its list: exactly the iterations at

@@ -1,4 +1,4 @@
-"""ctypes view of include/msf_abi.h, include/msf_initializer.h, include/msf_local_mapping.h and include/msf_pnp.h.  Loading fails loudly when libmsf.so is missing: there is no CPU fallback."""
+"""ctypes view of include/msf_abi.h, include/msf_initializer.h, include/msf_local_mapping.h, include/msf_pnp.h and include/msf_pose.h.  Loading fails loudly when libmsf.so is missing: there is no CPU fallback."""
 import ctypes as C
 import os
 
@@ -52,6 +52,9 @@ LOCAL_MAPPING_SYMBOLS = ["msf_local_mapping_version", "msf_new_points", "msf_new
 
 # every symbol include/msf_pnp.h declares (again a header and a version of its own)
 PNP_SYMBOLS = ["msf_pnp_version", "msf_pnp_ransac", "msf_pnp_ransac_device"]
+
+# every symbol include/msf_pose.h declares (again a header and a version of its own)
+POSE_SYMBOLS = ["msf_pose_version", "msf_pose_optimize", "msf_pose_optimize_device"]
 
 
 class Config(C.Structure):
@@ -139,6 +142,33 @@ def pnp_shapes(lists, n_iterations, max_records, cap):
     return {name: (lead[per] + tuple(cap if t == "cap" else t for t in tail), dt) for name, dt, per, tail in PNP_ARRAYS}
 
 
+class PoseParams(C.Structure):
+    """msf_pose_params: the frame's intrinsics and chi2Mono"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("fx", C.c_float), ("fy", C.c_float),
+                ("cx", C.c_float), ("cy", C.c_float), ("chi2", C.c_float)]
+
+
+# msf_pose_result's arrays in declaration order: name -> (dtype, per "list" / "round" / "it", trailing shape; "cap" = the lists' stride)
+POSE_ARRAYS = [("n_good", "int32", "list", ()), ("Tcw", "float32", "list", (12,)), ("outliers", "uint8", "list", ("cap",)),
+               ("n_edges", "int32", "list", ()), ("rounds_run", "int32", "list", ()), ("pose_f64", "float64", "list", (12,)),
+               ("round_pose_f64", "float64", "round", (12,)), ("round_n_bad", "int32", "round", ()),
+               ("round_iterations", "int32", "round", ()),
+               ("it_trials", "int32", "it", ()), ("it_lambda_in", "float64", "it", ()), ("it_lambda_out", "float64", "it", ()),
+               ("it_cost_in", "float64", "it", ()), ("it_cost_out", "float64", "it", ()), ("it_H", "float64", "it", (21,)),
+               ("it_b", "float64", "it", (6,)), ("it_pose_out", "float64", "it", (7,))]
+
+
+class PoseResult(C.Structure):
+    """msf_pose_result: host pointers for msf_pose_optimize, device pointers for msf_pose_optimize_device"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(a[0], C.c_void_p) for a in POSE_ARRAYS]
+
+
+def pose_shapes(lists, cap):
+    """-> {name: (shape, dtype name)} of msf_pose_result's arrays"""
+    lead = {"list": (lists,), "round": (lists, 4), "it": (lists, 4, 10)}
+    return {name: (lead[per] + tuple(cap if t == "cap" else t for t in tail), dt) for name, dt, per, tail in POSE_ARRAYS}
+
+
 VIEW_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4")])
 NEW_POINT_DTYPE = np.dtype([("match", "<i4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4")])
 MATCH_DTYPE = np.dtype([("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4")])
@@ -199,6 +229,10 @@ def load():
     L.msf_pnp_version.restype = C.c_int
     L.msf_pnp_ransac.argtypes = [vp, i32, vp, vp, C.POINTER(PnpParams), vp, C.POINTER(PnpResult)]
     L.msf_pnp_ransac_device.argtypes = [vp, i32, vp, vp, i32, vp, C.POINTER(PnpParams), vp, C.POINTER(PnpResult), vp]
+    L.msf_pose_version.restype = C.c_int
+    L.msf_pose_optimize.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(PoseParams), C.POINTER(PoseResult)]
+    L.msf_pose_optimize_device.argtypes = [vp, i32, vp, vp, i32, vp, vp, i64, vp, i64, C.POINTER(PoseParams),
+                                           C.POINTER(PoseResult), vp]
     L.msf_render_match_image.argtypes = [vp, C.POINTER(Image), C.POINTER(Image), vp, i32, vp, vp, vp, i64]
     L.msf_weights_info.argtypes = [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(i64)]
     L.msf_convert_weights.argtypes = [C.c_char_p, C.c_char_p]

@@ -1,0 +1,155 @@
+// hip_optimizer.h -- C++ host mirror of SLAM_PIPELINE::Optimizer::PoseOptimization (slam_pipeline/include/Optimizer.h,
+// slam_pipeline/src/Optimizer.cc:217-334) above the C ABI: the four Levenberg-Marquardt rounds and the chi2 flags are
+// msf_pose_optimize / msf_pose_optimize_device (include/msf_pose.h).
+//
+// The reference walks pFrame->mKeyPointMap, adds one edge per key point that has a map point, optimises, and writes
+// the flags (SetOutlier, :312-316) and the pose (SetPose, :331) back into the frame.  Here the caller gathers what the
+// edges are made of -- GetWorldPos() of each map point and the key point's pixel, in the order of its own index list --
+// and gets back the flags in that order, the pose in place and the return value nInitialCorrespondences - nBad.
+// With fewer than 3 correspondences the return is 0, the pose is untouched and every flag is false (:253, :285).
+//
+// Tracking::Relocalization (Tracking.cc:827) calls PoseOptimization once per candidate on PnPsolver's output:
+// PoseOptimizationBatch runs all candidates in ONE msf_pose_optimize_device call.
+//
+// Header-only and OpenCV-free, like hip_pnp_solver.h: a 3-D point is three floats, a pixel two, Tcw a row-major
+// float[16].  See INTEGRATION.md.
+#pragma once
+
+#ifndef __HIP_PLATFORM_AMD__
+#define __HIP_PLATFORM_AMD__ 1
+#endif
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "msf_pose.h"
+
+namespace msf {
+
+#ifndef MSF_POINT3F_DEFINED
+#define MSF_POINT3F_DEFINED
+struct Point3f {   // cv::Point3f
+  float x, y, z;
+};
+#endif
+
+#ifndef MSF_POINT2F_DEFINED
+#define MSF_POINT2F_DEFINED
+struct Point2f {   // cv::Point2f
+  float x, y;
+};
+#endif
+
+class Optimizer {
+ public:
+  // intrinsics = (fx, fy, cx, cy) of the frame; Tcw in: pFrame->mTcw, out: the optimised pose (rows 0..2 replaced, row 3
+  // set to 0 0 0 1, as Converter::toCvMat builds it); outliers[i]: mKeyPointMap.IsOutlier of correspondence i afterwards.
+  // -> nInitialCorrespondences - nBad; -1: the call failed and msf_last_error(handle) has the text (Tcw and outliers are
+  // left alone).
+  static int PoseOptimization(msf_handle* handle, const std::vector<Point3f>& points, const std::vector<Point2f>& pixels,
+                              const float intrinsics[4], float Tcw[16], std::vector<bool>& outliers, float chi2 = 5.991f) {
+    const int32_t n = static_cast<int32_t>(std::min(points.size(), pixels.size()));
+    const msf_pose_params prm = Params(intrinsics, chi2);
+    int32_t n_good = 0, rounds = 0;
+    float optimised[12];
+    std::vector<uint8_t> flags(n > 0 ? n : 1, 0);
+    msf_pose_result out;
+    std::memset(&out, 0, sizeof out);
+    out.struct_size = sizeof out;
+    out.n_good = &n_good, out.rounds_run = &rounds, out.Tcw = optimised, out.outliers = flags.data();
+    const int rc = msf_pose_optimize(handle, n, n ? &points[0].x : nullptr, n ? &pixels[0].x : nullptr, Tcw, nullptr, &prm, &out);
+    if (rc != MSF_OK) return -1;
+    Report(n, flags.data(), rounds, optimised, Tcw, outliers);
+    return n_good;
+  }
+
+  // One candidate of a batch: what PoseOptimization takes and gives, n_good its return.
+  struct Candidate {
+    const std::vector<Point3f>* points;
+    const std::vector<Point2f>* pixels;
+    float* Tcw;                   // [16], in-out
+    std::vector<bool>* outliers;  // out
+    int n_good;                   // out
+  };
+
+  // PoseOptimization of every candidate with ONE msf_pose_optimize_device call on a block allocated here.  The calling
+  // thread's current HIP device must be the handle's.  false: a failed call (nothing is written).
+  static bool PoseOptimizationBatch(msf_handle* handle, std::vector<Candidate>& candidates, const float intrinsics[4],
+                                    float chi2 = 5.991f) {
+    const size_t L = candidates.size();
+    if (!L) return true;
+    size_t cap = 1;
+    for (const Candidate& c : candidates) cap = std::max(cap, std::min(c.points->size(), c.pixels->size()));
+    std::vector<float> p3(L * cap * 3, 0.0f), p2(L * cap * 2, 0.0f), t0(L * 12);
+    std::vector<int32_t> n(L);
+    for (size_t l = 0; l < L; l++) {
+      const Candidate& c = candidates[l];
+      n[l] = static_cast<int32_t>(std::min(c.points->size(), c.pixels->size()));
+      if (n[l]) std::memcpy(&p3[l * cap * 3], c.points->data(), n[l] * sizeof(Point3f));
+      if (n[l]) std::memcpy(&p2[l * cap * 2], c.pixels->data(), n[l] * sizeof(Point2f));
+      std::memcpy(&t0[l * 12], c.Tcw, 48);
+    }
+    // one block: the inputs, then n_good, rounds_run, Tcw and the flags
+    const size_t sizes[] = {p3.size() * 4, p2.size() * 4, n.size() * 4, t0.size() * 4, L * 4, L * 4, L * 48, L * cap};
+    size_t off[9] = {0};
+    for (int k = 0; k < 8; k++) off[k + 1] = off[k] + ((sizes[k] + 255) & ~static_cast<size_t>(255));
+    char* base = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&base), off[8]) != hipSuccess) return false;
+    bool ok = hipMemcpy(base + off[0], p3.data(), sizes[0], hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(base + off[1], p2.data(), sizes[1], hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(base + off[2], n.data(), sizes[2], hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(base + off[3], t0.data(), sizes[3], hipMemcpyHostToDevice) == hipSuccess;
+    const msf_pose_params prm = Params(intrinsics, chi2);
+    msf_pose_result out;
+    std::memset(&out, 0, sizeof out);
+    out.struct_size = sizeof out;
+    out.n_good = reinterpret_cast<int32_t*>(base + off[4]);
+    out.rounds_run = reinterpret_cast<int32_t*>(base + off[5]);
+    out.Tcw = reinterpret_cast<float*>(base + off[6]);
+    out.outliers = reinterpret_cast<uint8_t*>(base + off[7]);
+    ok = ok && msf_pose_optimize_device(handle, static_cast<int32_t>(L), reinterpret_cast<const float*>(base + off[0]),
+                                        reinterpret_cast<const float*>(base + off[1]), static_cast<int32_t>(cap),
+                                        reinterpret_cast<const int32_t*>(base + off[2]),
+                                        reinterpret_cast<const float*>(base + off[3]), 12, nullptr, 0, &prm, &out,
+                                        nullptr) == MSF_OK;
+    std::vector<int32_t> n_good(L), rounds(L);
+    std::vector<float> tcw(L * 12);
+    std::vector<uint8_t> flags(L * cap);
+    void* host[] = {n_good.data(), rounds.data(), tcw.data(), flags.data()};
+    for (int k = 0; k < 4 && ok; k++) ok = hipMemcpy(host[k], base + off[4 + k], sizes[4 + k], hipMemcpyDeviceToHost) == hipSuccess;
+    hipFree(base);
+    if (!ok) return false;
+    for (size_t l = 0; l < L; l++) {
+      Candidate& c = candidates[l];
+      Report(n[l], &flags[l * cap], rounds[l], &tcw[l * 12], c.Tcw, *c.outliers);
+      c.n_good = n_good[l];
+    }
+    return true;
+  }
+
+ private:
+  static msf_pose_params Params(const float intrinsics[4], float chi2) {
+    msf_pose_params prm;
+    std::memset(&prm, 0, sizeof prm);
+    prm.struct_size = sizeof prm;
+    prm.fx = intrinsics[0], prm.fy = intrinsics[1], prm.cx = intrinsics[2], prm.cy = intrinsics[3];
+    prm.chi2 = chi2;
+    return prm;
+  }
+
+  // :312-333: the flags of every correspondence; the pose only when a round ran (:285 returns before SetPose)
+  static void Report(int32_t n, const uint8_t* flags, int32_t rounds, const float* optimised, float Tcw[16],
+                     std::vector<bool>& outliers) {
+    outliers.assign(n, false);
+    if (!rounds) return;
+    for (int32_t i = 0; i < n; i++) outliers[i] = flags[i] != 0;
+    std::memcpy(Tcw, optimised, 48);
+    Tcw[12] = Tcw[13] = Tcw[14] = 0.0f;
+    Tcw[15] = 1.0f;
+  }
+};
+
+}  // namespace msf

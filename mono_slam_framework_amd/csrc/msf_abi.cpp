@@ -16,8 +16,10 @@
 #include "msf_initializer.h"
 #include "msf_local_mapping.h"
 #include "msf_pnp.h"
+#include "msf_pose.h"
 #include "orb_pipeline.h"
 #include "pnp_pipeline.h"
+#include "pose_pipeline.h"
 #include "ransac_solve.h"
 #include "reconstruct_pipeline.h"
 #include "triangulate_pipeline.h"
@@ -109,6 +111,8 @@ struct msf_handle {
   // msf_pnp_ransac / msf_pnp_ransac_device workspace: the host call's list, sets and results; for the device call the
   // counts and poses that the second launch reads when the caller does not ask for them
   DevBuf<uint8_t> d_pnp;
+  // msf_pose_optimize workspace: the host call's list, entry pose, mask and results (the device call needs none)
+  DevBuf<uint8_t> d_pose;
   std::vector<msf_view> view_stage;   // [2][n]: the query's view once per pair, then the neighbours'
   // msf_render_match_image workspace: the RGB image (allocated once) and the match list + flags (grown on demand)
   DevBuf<uint8_t> d_render;      // [H][2 * W][3]
@@ -1441,6 +1445,136 @@ int msf_pnp_ransac_device(msf_handle* h, int32_t n_lists, const float* d_p3d, co
     if (int rc = plan_pnp(h, (size_t)n_lists, (size_t)cap, params, out, false, &p)) return rc;
     const msf::PnpLists in{d_p3d, d_p2d, cap, d_n, 0, d_sets};
     HIP_TRY(h, "pnp_ransac", msf::pnp_ransac(n_lists, in, pnp_params(params), p.out, cs.st));
+    return cs.finish();
+  });
+}
+
+namespace {
+
+// Where msf_pose_optimize keeps its device data: the list, and a piece for every result the caller asked for.
+struct PosePlan {
+  msf::PoseOut out{};
+  float* p3d = nullptr;
+  float* p2d = nullptr;
+  float* tcw0 = nullptr;
+  uint8_t* mask = nullptr;
+  size_t bytes = 0;
+  uint8_t* base = nullptr;
+};
+
+int plan_pose(msf_handle* h, size_t cap, bool with_mask, const msf_pose_result* want, PosePlan* p) {
+  constexpr size_t R = 4, I = 40;
+  return carve(h, h->d_pose, (size_t)1 << 16, "hipMalloc(pose workspace)", [&](msf::Carver& c) {
+    msf::PoseOut& o = p->out;
+    p->base = c.base;
+    p->p3d = c.take<float>(cap * 3);
+    p->p2d = c.take<float>(cap * 2);
+    p->tcw0 = c.take<float>(12);
+    p->mask = with_mask ? c.take<uint8_t>(cap) : nullptr;
+    o.n_good = c.take<int32_t>(1);
+    o.tcw = want->Tcw ? c.take<float>(12) : nullptr;
+    o.outliers = want->outliers ? c.take<uint8_t>(cap) : nullptr;
+    o.n_edges = want->n_edges ? c.take<int32_t>(1) : nullptr;
+    o.rounds_run = want->rounds_run ? c.take<int32_t>(1) : nullptr;
+    o.pose_f64 = want->pose_f64 ? c.take<double>(12) : nullptr;
+    o.round_pose_f64 = want->round_pose_f64 ? c.take<double>(R * 12) : nullptr;
+    o.round_n_bad = want->round_n_bad ? c.take<int32_t>(R) : nullptr;
+    o.round_iterations = want->round_iterations ? c.take<int32_t>(R) : nullptr;
+    o.it_trials = want->it_trials ? c.take<int32_t>(I) : nullptr;
+    o.it_lambda_in = want->it_lambda_in ? c.take<double>(I) : nullptr;
+    o.it_lambda_out = want->it_lambda_out ? c.take<double>(I) : nullptr;
+    o.it_cost_in = want->it_cost_in ? c.take<double>(I) : nullptr;
+    o.it_cost_out = want->it_cost_out ? c.take<double>(I) : nullptr;
+    o.it_H = want->it_H ? c.take<double>(I * 21) : nullptr;
+    o.it_b = want->it_b ? c.take<double>(I * 6) : nullptr;
+    o.it_pose_out = want->it_pose_out ? c.take<double>(I * 7) : nullptr;
+    p->bytes = c.off;
+  });
+}
+
+// nullptr when params and out are usable, else what is wrong with them
+const char* pose_fault(const msf_pose_params* prm, const msf_pose_result* out) {
+  if (!out || out->struct_size != sizeof(msf_pose_result)) return "out is NULL or out->struct_size is not sizeof(msf_pose_result)";
+  if (!prm || prm->struct_size != sizeof(msf_pose_params)) return "params is NULL or params->struct_size is not sizeof(msf_pose_params)";
+  if (std::isnan(prm->chi2)) return "chi2 must not be NaN";
+  if (!out->n_good) return "a required pointer is NULL (out->n_good)";
+  return nullptr;
+}
+
+}  // namespace
+
+int msf_pose_version(void) { return MSF_POSE_VERSION; }
+
+int msf_pose_optimize(msf_handle* h, int32_t n, const float* p3d, const float* p2d, const float* Tcw0,
+                      const uint8_t* mask, const msf_pose_params* params, msf_pose_result* out) {
+  return guarded(h, "msf_pose_optimize", [&]() -> int {
+    if (const char* fault = pose_fault(params, out)) return fail(h, MSF_ERR_INVALID_ARG, std::string("msf_pose_optimize: ") + fault);
+    if (n < 0) return fail(h, MSF_ERR_INVALID_ARG, "msf_pose_optimize: n is negative");
+    if (!Tcw0 || (n > 0 && (!p3d || !p2d))) return fail(h, MSF_ERR_INVALID_ARG, "msf_pose_optimize: a required pointer is NULL (p3d, p2d, Tcw0)");
+    CallScope cs{h};
+    if (int rc = cs.enter()) return rc;
+    const size_t cap = n > 0 ? (size_t)n : 1, count = (size_t)n;
+    PosePlan p;
+    if (int rc = plan_pose(h, cap, mask != nullptr, out, &p)) return rc;
+    hipStream_t st = cs.st;
+    Drain drain{st};
+    // what the kernel leaves alone comes back as 0, and an outlier byte outside the mask as the caller had it
+    HIP_TRY(h, "hipMemsetAsync", hipMemsetAsync(p.base, 0, p.bytes, st));
+    if (n > 0) {
+      HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.p3d, p3d, count * 12, hipMemcpyHostToDevice, st));
+      HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.p2d, p2d, count * 8, hipMemcpyHostToDevice, st));
+      if (mask) HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.mask, mask, count, hipMemcpyHostToDevice, st));
+      if (mask && out->outliers)
+        HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.out.outliers, out->outliers, count, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.tcw0, Tcw0, 48, hipMemcpyHostToDevice, st));
+    const msf::PoseLists in{p.p3d, p.p2d, (int32_t)cap, nullptr, n, p.tcw0, 0, p.mask, 0};
+    const msf::PoseParams prm{params->fx, params->fy, params->cx, params->cy, params->chi2};
+    HIP_TRY(h, "pose_optimize", msf::pose_optimize(1, in, prm, p.out, st));
+    const msf::PoseOut& d = p.out;
+    if (int rc = fetch(h, st, out->n_good, d.n_good, 4)) return rc;
+    if (int rc = fetch(h, st, out->Tcw, d.tcw, 48)) return rc;
+    if (int rc = fetch(h, st, out->outliers, d.outliers, count)) return rc;
+    if (int rc = fetch(h, st, out->n_edges, d.n_edges, 4)) return rc;
+    if (int rc = fetch(h, st, out->rounds_run, d.rounds_run, 4)) return rc;
+    if (int rc = fetch(h, st, out->pose_f64, d.pose_f64, 96)) return rc;
+    if (int rc = fetch(h, st, out->round_pose_f64, d.round_pose_f64, 4 * 96)) return rc;
+    if (int rc = fetch(h, st, out->round_n_bad, d.round_n_bad, 16)) return rc;
+    if (int rc = fetch(h, st, out->round_iterations, d.round_iterations, 16)) return rc;
+    if (int rc = fetch(h, st, out->it_trials, d.it_trials, 40 * 4)) return rc;
+    if (int rc = fetch(h, st, out->it_lambda_in, d.it_lambda_in, 40 * 8)) return rc;
+    if (int rc = fetch(h, st, out->it_lambda_out, d.it_lambda_out, 40 * 8)) return rc;
+    if (int rc = fetch(h, st, out->it_cost_in, d.it_cost_in, 40 * 8)) return rc;
+    if (int rc = fetch(h, st, out->it_cost_out, d.it_cost_out, 40 * 8)) return rc;
+    if (int rc = fetch(h, st, out->it_H, d.it_H, 40 * 21 * 8)) return rc;
+    if (int rc = fetch(h, st, out->it_b, d.it_b, 40 * 6 * 8)) return rc;
+    if (int rc = fetch(h, st, out->it_pose_out, d.it_pose_out, 40 * 7 * 8)) return rc;
+    drain.armed = false;
+    return cs.finish();
+  });
+}
+
+int msf_pose_optimize_device(msf_handle* h, int32_t n_lists, const float* d_p3d, const float* d_p2d, int32_t cap,
+                             const int32_t* d_n, const float* d_Tcw0, int64_t Tcw0_stride, const uint8_t* d_mask,
+                             int64_t mask_stride, const msf_pose_params* params, msf_pose_result* out, void* stream) {
+  return guarded(h, "msf_pose_optimize_device", [&]() -> int {
+    if (const char* fault = pose_fault(params, out))
+      return fail(h, MSF_ERR_INVALID_ARG, std::string("msf_pose_optimize_device: ") + fault);
+    if (n_lists < 0) return fail(h, MSF_ERR_INVALID_ARG, "msf_pose_optimize_device: n_lists is negative");
+    if (cap < 1) return fail(h, MSF_ERR_INVALID_ARG, "msf_pose_optimize_device: cap < 1");
+    if (Tcw0_stride < 0 || mask_stride < 0) return fail(h, MSF_ERR_INVALID_ARG, "msf_pose_optimize_device: a negative stride");
+    if (n_lists > 0 && (!d_p3d || !d_p2d || !d_n || !d_Tcw0))
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_pose_optimize_device: a required pointer is NULL (d_p3d, d_p2d, d_n, d_Tcw0)");
+    if (n_lists == 0) return MSF_OK;
+    CallScope cs{h};
+    if (int rc = cs.enter(stream)) return rc;
+    const msf::PoseLists in{d_p3d, d_p2d, cap, d_n, 0, d_Tcw0, Tcw0_stride, d_mask, mask_stride};
+    const msf::PoseParams prm{params->fx, params->fy, params->cx, params->cy, params->chi2};
+    const msf::PoseOut o{out->n_good, out->Tcw, out->outliers, out->n_edges, out->rounds_run, out->pose_f64,
+                         out->round_pose_f64, out->round_n_bad, out->round_iterations, out->it_trials,
+                         out->it_lambda_in, out->it_lambda_out, out->it_cost_in, out->it_cost_out, out->it_H, out->it_b,
+                         out->it_pose_out};
+    HIP_TRY(h, "pose_optimize", msf::pose_optimize(n_lists, in, prm, o, cs.st));
     return cs.finish();
   });
 }

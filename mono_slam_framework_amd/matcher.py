@@ -461,6 +461,75 @@ class _Matcher:
                                                   C.byref(res), stream))
         return d
 
+    @staticmethod
+    def _pose_params(K, chi2):
+        fx, fy, cx, cy = K
+        return _lib.PoseParams(struct_size=C.sizeof(_lib.PoseParams), fx=fx, fy=fy, cx=cx, cy=cy, chi2=chi2)
+
+    def pose_optimize(self, p3d, p2d, K, Tcw0, mask=None, chi2=5.991, diagnostics=True):
+        """Optimizer::PoseOptimization on one list (Optimizer.cc:217-334): p3d f32 [n, 3] (GetWorldPos()), p2d f32 [n, 2]
+        (the key points' pixels), K = (fx, fy, cx, cy), Tcw0 f32 [12] or [3, 4] (rows 0..2 of mTcw), mask uint8 [n] or
+        None (non-zero: the correspondence is an edge).  -> dict: n_good, n_edges, rounds_run (ints), Tcw f32 [12],
+        pose_f64 [12], outliers uint8 [n] (0 outside the mask), and with `diagnostics` the per-round arrays [4, ...]
+        and per-iteration arrays [4, 10, ...] of msf_pose_result."""
+        p3 = np.ascontiguousarray(p3d, np.float32).reshape(-1, 3)
+        p2 = np.ascontiguousarray(p2d, np.float32).reshape(-1, 2)
+        t0 = np.ascontiguousarray(Tcw0, np.float32).reshape(12)
+        n = len(p3)
+        assert len(p2) == n
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(mask, np.uint8).reshape(n)
+        d = {k: np.zeros(shape, dt) for k, (shape, dt) in _lib.pose_shapes(1, max(n, 1)).items()}
+        if not diagnostics:
+            for name, _, per, _ in _lib.POSE_ARRAYS:
+                if per != "list":
+                    del d[name]
+        res = _fill(_lib.PoseResult(), d)
+        prm = self._pose_params(K, chi2)
+        self._check(self._L.msf_pose_optimize(self._h, n, p3.ctypes.data, p2.ctypes.data, t0.ctypes.data,
+                                              m.ctypes.data if m is not None else None, C.byref(prm), C.byref(res)))
+        out = {k: v[0] for k, v in d.items()}
+        for k in ("n_good", "n_edges", "rounds_run"):
+            out[k] = int(out[k])
+        out["outliers"] = out["outliers"][:n]
+        return out
+
+    def pose_optimize_device(self, d_p3d, d_p2d, d_n, K, d_Tcw0, d_mask=None, chi2=5.991, Tcw0_stride=12,
+                             mask_stride=None, out=None, diagnostics=True, stream=None):
+        """The same for a batch in device memory: d_p3d f32 [L, cap, 3], d_p2d f32 [L, cap, 2], d_n int32 [L] (negative:
+        no valid list), d_Tcw0 f32 with list l's 12 floats at element l * Tcw0_stride, d_mask uint8 with list l's bytes
+        at l * mask_stride (default cap) or None: a view into Tcw_refined / inliers_refined of pnp_ransac_device's result
+        can be passed with its strides.  -> dict of CUDA tensors with a leading L, named and shaped as msf_pose_result
+        says; without `diagnostics` only the per-list arrays.  `out`: tensors to write into instead of fresh zeros.
+        One launch, asynchronous on `stream` (None = handle stream + sync)."""
+        import torch
+        assert d_p3d.is_cuda and d_p2d.is_cuda and d_n.is_cuda and d_p3d.is_contiguous() and d_p2d.is_contiguous()
+        assert d_p3d.dtype == torch.float32 and d_p2d.dtype == torch.float32 and d_n.dtype == torch.int32
+        L, cap = d_p3d.shape[0], d_p3d.shape[1]
+        assert tuple(d_p3d.shape) == (L, cap, 3) and tuple(d_p2d.shape) == (L, cap, 2) and d_n.numel() == L
+        assert d_Tcw0.is_cuda and d_Tcw0.dtype == torch.float32 and Tcw0_stride >= 0
+        assert L == 0 or d_Tcw0.untyped_storage().nbytes() // 4 - d_Tcw0.storage_offset() >= (L - 1) * Tcw0_stride + 12
+        if d_mask is not None:
+            mask_stride = cap if mask_stride is None else mask_stride
+            assert d_mask.is_cuda and d_mask.dtype == torch.uint8 and mask_stride >= 0
+            assert L == 0 or d_mask.untyped_storage().nbytes() - d_mask.storage_offset() >= (L - 1) * mask_stride + cap
+        d = out
+        if d is None:
+            z = _zeros_on(d_p3d.device)
+            d = {k: z(shape, dt) for k, (shape, dt) in _lib.pose_shapes(L, cap).items()}
+            if not diagnostics:
+                for name, _, per, _ in _lib.POSE_ARRAYS:
+                    if per != "list":
+                        del d[name]
+        res = _fill(_lib.PoseResult(), d)
+        prm = self._pose_params(K, chi2)
+        self._check(self._L.msf_pose_optimize_device(self._h, L, d_p3d.data_ptr(), d_p2d.data_ptr(), cap, d_n.data_ptr(),
+                                                     d_Tcw0.data_ptr(), Tcw0_stride,
+                                                     d_mask.data_ptr() if d_mask is not None else None,
+                                                     mask_stride or 0, C.byref(prm), C.byref(res), stream))
+        return d
+
     def render_match_image(self, frame1, frame2, matches, has_mp1=None, has_mp2=None):
         """Tracking::CreateCurrentMatchImage (Tracking.cc:899-940) -> uint8 [H, 2W, 3]."""
         a, b = self._image(frame1), self._image(frame2)
