@@ -85,12 +85,20 @@ class MotionParams(C.Structure):
                 ("min_triangulated", C.c_int32), ("min_parallax", C.c_float)]
 
 
+# The result structs' arrays in declaration order: (name, dtype, per, trailing shape) with `per` the leading unit after
+# [n_lists] ("list": none) and "cap" the lists' stride; csrc/result_arrays.h holds the same tables for the library
+# (tests/test_result_arrays_host.py compares them).
+MOTION_ARRAYS = [("ok", "int32", "list", ()), ("model", "int32", "list", ()), ("R21", "float32", "list", (9,)),
+                 ("t21", "float32", "list", (3,)), ("points", "float32", "list", ("cap", 3)),
+                 ("triangulated", "uint8", "list", ("cap",)), ("n_cand", "int32", "list", ()),
+                 ("cand_R", "float32", "list", (8, 9)), ("cand_t", "float32", "list", (8, 3)),
+                 ("cand_good", "int32", "list", (8,)), ("cand_parallax", "float32", "list", (8,)),
+                 ("winner", "int32", "list", ())]
+
+
 class MotionResult(C.Structure):
     """msf_motion_result: host pointers for msf_reconstruct, device pointers [n_lists] for msf_reconstruct_device"""
-    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("ok", C.c_void_p), ("model", C.c_void_p),
-                ("R21", C.c_void_p), ("t21", C.c_void_p), ("points", C.c_void_p), ("triangulated", C.c_void_p),
-                ("n_cand", C.c_void_p), ("cand_R", C.c_void_p), ("cand_t", C.c_void_p), ("cand_good", C.c_void_p),
-                ("cand_parallax", C.c_void_p), ("winner", C.c_void_p)]
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(a[0], C.c_void_p) for a in MOTION_ARRAYS]
 
 
 class View(C.Structure):
@@ -104,11 +112,16 @@ class NewPointsParams(C.Structure):
                 ("chi2", C.c_double)]
 
 
+NEW_POINT_DTYPE = np.dtype([("match", "<i4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4")])
+NEW_POINTS_ARRAYS = [("n_new", "int32", "list", ()), ("packed", NEW_POINT_DTYPE, "list", ("cap",)),
+                     ("status", "uint8", "list", ("cap",)), ("points", "float32", "list", ("cap", 3)),
+                     ("hom", "float32", "list", ("cap", 4)), ("cos_parallax", "float64", "list", ("cap",))]
+
+
 class NewPointsResult(C.Structure):
     """msf_new_points_result: host pointers for msf_new_points / msf_create_map_points, device pointers for
     msf_new_points_device"""
-    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_new", C.c_void_p), ("packed", C.c_void_p),
-                ("status", C.c_void_p), ("points", C.c_void_p), ("hom", C.c_void_p), ("cos_parallax", C.c_void_p)]
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(a[0], C.c_void_p) for a in NEW_POINTS_ARRAYS]
 
 
 class PnpParams(C.Structure):
@@ -170,7 +183,6 @@ def pose_shapes(lists, cap):
 
 
 VIEW_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4")])
-NEW_POINT_DTYPE = np.dtype([("match", "<i4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4")])
 MATCH_DTYPE = np.dtype([("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4")])
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("response", "<f4"), ("angle", "<f4"),
                      ("octave", "<i4"), ("lx", "<i4"), ("ly", "<i4"), ("fast_score", "<i4")])

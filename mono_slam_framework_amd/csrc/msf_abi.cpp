@@ -22,6 +22,7 @@
 #include "pose_pipeline.h"
 #include "ransac_solve.h"
 #include "reconstruct_pipeline.h"
+#include "result_arrays.h"
 #include "triangulate_pipeline.h"
 #include "weights_io.h"
 
@@ -240,6 +241,38 @@ int fetch(msf_handle* h, hipStream_t st, void* dst, const void* src, size_t byte
   if (!dst || !bytes) return MSF_OK;
   HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
   return MSF_OK;
+}
+
+// The result arrays of one list that `out` has a pointer for, from their device copies `dev`: copy_result()
+// (result_arrays.h) over the struct's table, with fetch() as the copier.
+template <class S, size_t N>
+int fetch_result(msf_handle* h, hipStream_t st, const msf::ResultArray (&table)[N], const S& dev, const S& out,
+                 const msf::Extent& e) {
+  return msf::copy_result(table, dev, out, e,
+                          [&](void* dst, const void* src, size_t bytes) { return fetch(h, st, dst, src, bytes); });
+}
+
+// The kernels' Out structs from a result struct of device pointers: the caller's (the _device entry points) or the
+// one carve_result() filled (the host entry points).
+msf::MotionOut to_out(const msf_motion_result& r) {   // n_inliers is no result: the entry point adds its piece
+  return msf::MotionOut{r.model, nullptr, r.n_cand, r.cand_R, r.cand_t, r.cand_good, r.cand_parallax, r.winner, r.ok,
+                        r.R21, r.t21, r.points, r.triangulated};
+}
+
+msf::NewPointOut to_out(const msf_new_points_result& r) {
+  return msf::NewPointOut{r.n_new, r.packed, r.status, r.points, r.hom, r.cos_parallax};
+}
+
+msf::PnpOut to_out(const msf_pnp_result& r) {
+  return msf::PnpOut{r.n_records, r.counts, r.iteration, r.n_inliers, r.refined_ok, r.n_refined, r.Tcw_best, r.Tcw_refined,
+                     r.inliers_best, r.inliers_refined, r.sets, r.pose_f64, r.cws, r.ut_tail, r.betas, r.rep_errors,
+                     r.pca, r.rec_pose_f64, r.rec_cws, r.rec_ut_tail, r.rec_betas, r.rec_rep_errors, r.rec_pca};
+}
+
+msf::PoseOut to_out(const msf_pose_result& r) {
+  return msf::PoseOut{r.n_good, r.Tcw, r.outliers, r.n_edges, r.rounds_run, r.pose_f64, r.round_pose_f64, r.round_n_bad,
+                      r.round_iterations, r.it_trials, r.it_lambda_in, r.it_lambda_out, r.it_cost_in, r.it_cost_out,
+                      r.it_H, r.it_b, r.it_pose_out};
 }
 
 constexpr int kFrameCacheSlots = 64;   // default capacity of the transparent frame cache (MSF_FRAME_CACHE_SLOTS overrides)
@@ -968,40 +1001,13 @@ int msf_find_models_device(msf_handle* h, int32_t n_lists, const msf_match* d_ma
 // ---- msf_initializer.h: the tail of Initializer::Initialize ----
 namespace {
 
-// The device arrays of one reconstruct call: the caller's where it gave one, else a piece of the handle's workspace.
+// What a reconstruct call keeps in the workspace besides its result arrays (result_arrays.h: kMotionArrays).
 struct ReconstructPlan {
-  msf::MotionOut out{};
+  int32_t* n_inliers = nullptr;   // MotionOut::n_inliers [n_lists]: handed from launch to launch, no result
   msf_match* matches = nullptr;   // host call only: the list, its inlier flags and its matrix
   uint8_t* inliers = nullptr;
   float* m21 = nullptr;
 };
-
-// user: the device pointers the caller supplied (the host entry point passes an empty struct and gets a piece of the
-// workspace for every output, the list included).  points / triangulated are only produced where somebody reads them.
-int plan_reconstruct(msf_handle* h, int n_lists, int cap, bool host_call, const msf_motion_result* user,
-                     const msf_motion_result* wanted, ReconstructPlan* p) {
-  const size_t L = (size_t)n_lists;
-  const bool want_points = host_call && wanted->points, want_tri = host_call && wanted->triangulated;
-  return carve(h, h->d_rc, (size_t)1 << 16, "hipMalloc(reconstruct workspace)", [&](msf::Carver& c) {
-    msf::MotionOut& o = p->out;
-    o.ok = c.take(user->ok, L);
-    o.model = c.take(user->model, L);
-    o.n_inliers = c.take<int32_t>(L);
-    o.n_cand = c.take(user->n_cand, L);
-    o.cand_R = c.take(user->cand_R, L * 72);
-    o.cand_t = c.take(user->cand_t, L * 24);
-    o.cand_good = c.take(user->cand_good, L * 8);
-    o.cand_parallax = c.take(user->cand_parallax, L * 8);
-    o.winner = c.take(user->winner, L);
-    o.R21 = c.take(user->R21, L * 9);
-    o.t21 = c.take(user->t21, L * 3);
-    o.points = !host_call ? user->points : want_points ? c.take<float>(L * cap * 3) : nullptr;
-    o.triangulated = !host_call ? user->triangulated : want_tri ? c.take<uint8_t>(L * cap) : nullptr;
-    p->matches = host_call ? c.take<msf_match>(cap) : nullptr;
-    p->inliers = host_call ? c.take<uint8_t>(cap) : nullptr;
-    p->m21 = host_call ? c.take<float>(9) : nullptr;
-  });
-}
 
 // nullptr when the parameters are usable, else what is wrong with them
 const char* motion_params_fault(const msf_motion_params* prm) {
@@ -1051,9 +1057,19 @@ int msf_reconstruct(msf_handle* h, int32_t model, const float* m21, int32_t n_ma
     CallScope cs{h};
     if (int rc = cs.enter()) return rc;
     const int cap = n_matches > 0 ? n_matches : 1;
-    const msf_motion_result none{};
+    const size_t units[] = {1};
+    msf_motion_result dev{};
     ReconstructPlan p;
-    if (int rc = plan_reconstruct(h, 1, cap, true, &none, out, &p)) return rc;
+    if (int rc = carve(h, h->d_rc, (size_t)1 << 16, "hipMalloc(reconstruct workspace)", [&](msf::Carver& c) {
+          msf::carve_result(c, msf::kMotionArrays, units, (size_t)cap, nullptr, *out, &dev);
+          p.n_inliers = c.take<int32_t>(1);
+          p.matches = c.take<msf_match>(cap);
+          p.inliers = c.take<uint8_t>(cap);
+          p.m21 = c.take<float>(9);
+        }))
+      return rc;
+    msf::MotionOut o = to_out(dev);
+    o.n_inliers = p.n_inliers;
     hipStream_t st = cs.st;
     Drain drain{st};
     if (n_matches > 0) {
@@ -1069,19 +1085,9 @@ int msf_reconstruct(msf_handle* h, int32_t model, const float* m21, int32_t n_ma
     in.forced_model = model;
     in.m21[model] = p.m21;
     in.inliers[model] = p.inliers;
-    HIP_TRY(h, "reconstruct_motion", msf::reconstruct_motion(1, in, motion_params(params), p.out, st));
-    if (int rc = fetch(h, st, out->ok, p.out.ok, 4)) return rc;
-    if (int rc = fetch(h, st, out->model, p.out.model, 4)) return rc;
-    if (int rc = fetch(h, st, out->R21, p.out.R21, 9 * 4)) return rc;
-    if (int rc = fetch(h, st, out->t21, p.out.t21, 3 * 4)) return rc;
-    if (int rc = fetch(h, st, out->points, p.out.points, (size_t)n_matches * 12)) return rc;
-    if (int rc = fetch(h, st, out->triangulated, p.out.triangulated, (size_t)n_matches)) return rc;
-    if (int rc = fetch(h, st, out->n_cand, p.out.n_cand, 4)) return rc;
-    if (int rc = fetch(h, st, out->cand_R, p.out.cand_R, 72 * 4)) return rc;
-    if (int rc = fetch(h, st, out->cand_t, p.out.cand_t, 24 * 4)) return rc;
-    if (int rc = fetch(h, st, out->cand_good, p.out.cand_good, 8 * 4)) return rc;
-    if (int rc = fetch(h, st, out->cand_parallax, p.out.cand_parallax, 8 * 4)) return rc;
-    if (int rc = fetch(h, st, out->winner, p.out.winner, 4)) return rc;
+    HIP_TRY(h, "reconstruct_motion", msf::reconstruct_motion(1, in, motion_params(params), o, st));
+    const msf::Extent all{0, (size_t)cap, (size_t)cap, (size_t)n_matches, units, units};
+    if (int rc = fetch_result(h, st, msf::kMotionArrays, dev, *out, all)) return rc;
     drain.armed = false;
     return cs.finish();   // the one wait of the call
   });
@@ -1111,8 +1117,16 @@ int msf_reconstruct_device(msf_handle* h, int32_t n_lists, const msf_match* d_ma
     if (n_lists == 0) return MSF_OK;
     CallScope cs{h};
     if (int rc = cs.enter(stream)) return rc;
+    const size_t units[] = {(size_t)n_lists};
+    msf_motion_result dev{};
     ReconstructPlan p;
-    if (int rc = plan_reconstruct(h, n_lists, cap_per_pair, false, out, out, &p)) return rc;
+    if (int rc = carve(h, h->d_rc, (size_t)1 << 16, "hipMalloc(reconstruct workspace)", [&](msf::Carver& c) {
+          msf::carve_result(c, msf::kMotionArrays, units, (size_t)cap_per_pair, out, *out, &dev);
+          p.n_inliers = c.take<int32_t>(n_lists);
+        }))
+      return rc;
+    msf::MotionOut o = to_out(dev);
+    o.n_inliers = p.n_inliers;
     msf::MotionLists in{};
     in.matches = d_matches;
     in.cap = cap_per_pair;
@@ -1125,44 +1139,31 @@ int msf_reconstruct_device(msf_handle* h, int32_t n_lists, const msf_match* d_ma
       in.best[m] = res[m]->best;
       in.inliers[m] = res[m]->best_inliers;
     }
-    HIP_TRY(h, "reconstruct_motion", msf::reconstruct_motion(n_lists, in, motion_params(params), p.out, cs.st));
+    HIP_TRY(h, "reconstruct_motion", msf::reconstruct_motion(n_lists, in, motion_params(params), o, cs.st));
     return cs.finish();
   });
 }
 
 namespace {
 
-// Where the host entry points of msf_local_mapping.h keep their device data: [lists] views of either side, every
-// output of the kernel with the lists' stride `cap`, and (with_list) one list of `cap` matches.
+// What the host entry points of msf_local_mapping.h keep in the workspace besides their result arrays
+// (result_arrays.h: kNewPointsArrays): [lists] views of either side and, for msf_new_points, the list.
 struct NewPointsPlan {
-  msf::NewPointOut out{};
   msf_view* view1 = nullptr;
   msf_view* view2 = nullptr;
   msf_match* matches = nullptr;
 };
 
-int plan_new_points(msf_handle* h, size_t lists, size_t cap, bool with_list, NewPointsPlan* p) {
-  return carve(h, h->d_lm, (size_t)1 << 16, "hipMalloc(new points workspace)", [&](msf::Carver& c) {
-    p->view1 = c.take<msf_view>(lists);
-    p->view2 = c.take<msf_view>(lists);
-    p->out.n_new = c.take<int32_t>(lists);
-    p->out.packed = c.take<msf_new_point>(lists * cap);
-    p->out.status = c.take<uint8_t>(lists * cap);
-    p->out.points = c.take<float>(lists * cap * 3);
-    p->out.hom = c.take<float>(lists * cap * 4);
-    p->out.cos_parallax = c.take<double>(lists * cap);
-    p->matches = with_list ? c.take<msf_match>(cap) : nullptr;
-  });
-}
-
-// the kernel writes only what somebody reads
-void keep_wanted(msf::NewPointOut* dev, const msf_new_points_result* wanted) {
-  if (!wanted->packed) dev->packed = nullptr;
-  if (!wanted->status) dev->status = nullptr;
-  if (!wanted->points) dev->points = nullptr;
-  if (!wanted->hom) dev->hom = nullptr;
-  if (!wanted->cos_parallax) dev->cos_parallax = nullptr;
-}
+// The copy-back of the host entry points goes in two: n_new and the per-match arrays up to the list's end, then --
+// once the count is on the host -- the first n_new records of packed.
+struct NewPointsWanted {
+  msf_new_points_result rows, records{};
+  explicit NewPointsWanted(const msf_new_points_result& out) : rows(out) {
+    rows.n_new = nullptr;   // fetched first, by the entry point
+    rows.packed = nullptr;
+    records.packed = out.packed;
+  }
+};
 
 // nullptr when params and out are usable, else what is wrong with them
 const char* new_points_fault(const msf_new_points_params* prm, const msf_new_points_result* out) {
@@ -1171,19 +1172,6 @@ const char* new_points_fault(const msf_new_points_params* prm, const msf_new_poi
   if (std::isnan(prm->max_cos_parallax) || std::isnan(prm->chi2)) return "max_cos_parallax and chi2 must not be NaN";
   if (!out->n_new) return "a required pointer is NULL (out->n_new)";
   return nullptr;
-}
-
-// Rows [0, w) of list `i` of every wanted per-match array and the first n_new records, device stride dcap -> host
-// stride hcap, on `st`.
-int fetch_new_points(msf_handle* h, const msf::NewPointOut& dev, size_t dcap, const msf_new_points_result* out, size_t hcap,
-                     size_t i, size_t w, int32_t n_new, hipStream_t st) {
-  const size_t hi = i * hcap, di = i * dcap, records = n_new > 0 ? (size_t)n_new : 0;
-  if (int rc = fetch(h, st, from(out->packed, hi), from(dev.packed, di), records * sizeof(msf_new_point))) return rc;
-  if (int rc = fetch(h, st, from(out->status, hi), from(dev.status, di), w)) return rc;
-  if (int rc = fetch(h, st, from(out->points, hi * 3), from(dev.points, di * 3), w * 12)) return rc;
-  if (int rc = fetch(h, st, from(out->hom, hi * 4), from(dev.hom, di * 4), w * 16)) return rc;
-  if (int rc = fetch(h, st, from(out->cos_parallax, hi), from(dev.cos_parallax, di), w * 8)) return rc;
-  return MSF_OK;
 }
 
 }  // namespace
@@ -1201,9 +1189,16 @@ int msf_new_points(msf_handle* h, int32_t n_matches, const msf_match* matches, c
     CallScope cs{h};
     if (int rc = cs.enter()) return rc;
     const int cap = n_matches > 0 ? n_matches : 1;
+    const size_t units[] = {1};
+    msf_new_points_result dev{};
     NewPointsPlan p;
-    if (int rc = plan_new_points(h, 1, (size_t)cap, true, &p)) return rc;
-    keep_wanted(&p.out, out);
+    if (int rc = carve(h, h->d_lm, (size_t)1 << 16, "hipMalloc(new points workspace)", [&](msf::Carver& c) {
+          p.view1 = c.take<msf_view>(1);
+          p.view2 = c.take<msf_view>(1);
+          msf::carve_result(c, msf::kNewPointsArrays, units, (size_t)cap, nullptr, *out, &dev);
+          p.matches = c.take<msf_match>(cap);
+        }))
+      return rc;
     hipStream_t st = cs.st;
     Drain drain{st};
     if (n_matches > 0)
@@ -1211,12 +1206,15 @@ int msf_new_points(msf_handle* h, int32_t n_matches, const msf_match* matches, c
     HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.view1, view1, sizeof(msf_view), hipMemcpyHostToDevice, st));
     HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.view2, view2, sizeof(msf_view), hipMemcpyHostToDevice, st));
     const msf::NewPointLists in{p.matches, cap, cap, nullptr, n_matches, p.view1, p.view2};
-    HIP_TRY(h, "new_points", msf::new_points(1, in, new_point_params(params), p.out, st));
-    if (int rc = fetch(h, st, out->n_new, p.out.n_new, 4)) return rc;
-    if (int rc = fetch_new_points(h, p.out, (size_t)cap, out, (size_t)cap, 0, (size_t)n_matches, 0, st)) return rc;
+    HIP_TRY(h, "new_points", msf::new_points(1, in, new_point_params(params), to_out(dev), st));
+    const NewPointsWanted want(*out);
+    msf::Extent e{0, (size_t)cap, (size_t)cap, (size_t)n_matches, units, units};
+    if (int rc = fetch(h, st, out->n_new, dev.n_new, sizeof *out->n_new)) return rc;
+    if (int rc = fetch_result(h, st, msf::kNewPointsArrays, dev, want.rows, e)) return rc;
     if (out->packed) {   // the first n_new records: the count has to arrive first
       HIP_TRY(h, "hipStreamSynchronize", hipStreamSynchronize(st));
-      if (int rc = fetch_new_points(h, p.out, (size_t)cap, out, (size_t)cap, 0, 0, out->n_new[0], st)) return rc;
+      e.n = out->n_new[0] > 0 ? (size_t)out->n_new[0] : 0;
+      if (int rc = fetch_result(h, st, msf::kNewPointsArrays, dev, want.records, e)) return rc;
     }
     drain.armed = false;
     return cs.finish();
@@ -1238,8 +1236,7 @@ int msf_new_points_device(msf_handle* h, int32_t n_lists, const msf_match* d_mat
     CallScope cs{h};
     if (int rc = cs.enter(stream)) return rc;
     const msf::NewPointLists in{d_matches, cap_per_pair, cap_per_pair, d_n_out, 0, d_view1, d_view2};
-    const msf::NewPointOut dev{out->n_new, out->packed, out->status, out->points, out->hom, out->cos_parallax};
-    HIP_TRY(h, "new_points", msf::new_points(n_lists, in, new_point_params(params), dev, cs.st));
+    HIP_TRY(h, "new_points", msf::new_points(n_lists, in, new_point_params(params), to_out(*out), cs.st));
     return cs.finish();
   });
 }
@@ -1259,9 +1256,16 @@ int msf_create_map_points(msf_handle* h, int32_t query_slot, const msf_view* que
     CallScope cs{h};
     if (int rc = cs.enter()) return rc;
     hipStream_t st = cs.st;
+    // sized for max_batch_pairs lists whatever n is: the pieces stay where they are from call to call
+    const size_t units[] = {(size_t)h->cfg.max_batch_pairs}, one[] = {1};
+    msf_new_points_result dev{};
     NewPointsPlan p;
-    if (int rc = plan_new_points(h, (size_t)h->cfg.max_batch_pairs, (size_t)h->stage_cap, false, &p)) return rc;
-    keep_wanted(&p.out, out);
+    if (int rc = carve(h, h->d_lm, (size_t)1 << 16, "hipMalloc(new points workspace)", [&](msf::Carver& c) {
+          p.view1 = c.take<msf_view>(units[0]);
+          p.view2 = c.take<msf_view>(units[0]);
+          msf::carve_result(c, msf::kNewPointsArrays, units, (size_t)h->stage_cap, nullptr, *out, &dev);
+        }))
+      return rc;
     Drain drain{st};
     h->view_stage.resize((size_t)2 * n);
     for (int i = 0; i < n; i++) { h->view_stage[i] = *query_view; h->view_stage[n + i] = views[i]; }
@@ -1270,19 +1274,22 @@ int msf_create_map_points(msf_handle* h, int32_t query_slot, const msf_view* que
     if (int rc = launch_one_to_many(h, query_slot, n, slots, st)) return rc;
     const int limit = cap_per_pair < h->stage_cap ? cap_per_pair : h->stage_cap;
     const msf::NewPointLists in{h->d_out, h->stage_cap, limit, h->d_n, 0, p.view1, p.view2};
-    HIP_TRY(h, "new_points", msf::new_points(n, in, new_point_params(params), p.out, st));
-    if (int rc = fetch(h, st, num_matches, h->d_n, (size_t)n * 4)) return rc;
-    if (int rc = fetch(h, st, out->n_new, p.out.n_new, (size_t)n * 4)) return rc;
+    HIP_TRY(h, "new_points", msf::new_points(n, in, new_point_params(params), to_out(dev), st));
+    if (int rc = fetch(h, st, num_matches, h->d_n, (size_t)n * sizeof *num_matches)) return rc;
+    if (int rc = fetch(h, st, out->n_new, dev.n_new, (size_t)n * sizeof *out->n_new)) return rc;
     HIP_TRY(h, "hipStreamSynchronize", hipStreamSynchronize(st));
     // the copy-back: the counts say how much of every list there is to fetch
     bool capacity = false;
+    const NewPointsWanted want(*out);
     for (int i = 0; i < n; i++) {
       const int w = deliverable(h, num_matches[i], cap_per_pair, &capacity);
       if (int rc = fetch(h, st, from(out_matches, (size_t)i * cap_per_pair), h->d_out + (size_t)i * h->stage_cap,
                          (size_t)w * sizeof(msf_match)))
         return rc;
-      if (int rc = fetch_new_points(h, p.out, (size_t)h->stage_cap, out, (size_t)cap_per_pair, (size_t)i, (size_t)w, out->n_new[i], st))
-        return rc;
+      msf::Extent e{(size_t)i, (size_t)h->stage_cap, (size_t)cap_per_pair, (size_t)w, one, one};
+      if (int rc = fetch_result(h, st, msf::kNewPointsArrays, dev, want.rows, e)) return rc;
+      e.n = out->n_new[i] > 0 ? (size_t)out->n_new[i] : 0;
+      if (int rc = fetch_result(h, st, msf::kNewPointsArrays, dev, want.records, e)) return rc;
     }
     drain.armed = false;
     if (int rc = cs.finish()) return rc;
@@ -1292,58 +1299,13 @@ int msf_create_map_points(msf_handle* h, int32_t query_slot, const msf_view* que
 
 namespace {
 
-// Where an msf_pnp.h call keeps its device data.  `given`: the caller's device arrays (msf_pnp_ransac_device), kept
-// where they are; null: everything is carved (msf_pnp_ransac) and copied back.
+// What msf_pnp_ransac keeps in the workspace besides its result arrays (result_arrays.h: kPnpArrays): the list and
+// the caller's sets.
 struct PnpPlan {
-  msf::PnpOut out{};
   float* p3d = nullptr;
   float* p2d = nullptr;
   int32_t* sets_in = nullptr;
 };
-
-int plan_pnp(msf_handle* h, size_t lists, size_t cap, const msf_pnp_params* prm, const msf_pnp_result* given,
-             bool with_sets, PnpPlan* p) {
-  const size_t hyps = lists * (size_t)prm->n_iterations, recs = lists * (size_t)prm->max_records;
-  return carve(h, h->d_pnp, (size_t)1 << 16, "hipMalloc(pnp workspace)", [&](msf::Carver& c) {
-    msf::PnpOut& o = p->out;
-    if (given) {
-      o = msf::PnpOut{given->n_records, given->counts, given->iteration, given->n_inliers, given->refined_ok,
-                      given->n_refined, given->Tcw_best, given->Tcw_refined, given->inliers_best, given->inliers_refined,
-                      given->sets, given->pose_f64, given->cws, given->ut_tail, given->betas, given->rep_errors, given->pca,
-                      given->rec_pose_f64, given->rec_cws, given->rec_ut_tail, given->rec_betas, given->rec_rep_errors,
-                      given->rec_pca};
-      o.counts = c.take(o.counts, hyps);
-      o.pose_f64 = c.take(o.pose_f64, hyps * 12);
-      return;
-    }
-    p->p3d = c.take<float>(cap * 3);
-    p->p2d = c.take<float>(cap * 2);
-    p->sets_in = with_sets ? c.take<int32_t>(hyps * 4) : nullptr;
-    o.n_records = c.take<int32_t>(lists);
-    o.counts = c.take<int32_t>(hyps);
-    o.iteration = c.take<int32_t>(recs);
-    o.n_inliers = c.take<int32_t>(recs);
-    o.refined_ok = c.take<int32_t>(recs);
-    o.n_refined = c.take<int32_t>(recs);
-    o.tcw_best = c.take<float>(recs * 12);
-    o.tcw_refined = c.take<float>(recs * 12);
-    o.inliers_best = c.take<uint8_t>(recs * cap);
-    o.inliers_refined = c.take<uint8_t>(recs * cap);
-    o.sets = c.take<int32_t>(hyps * 4);
-    o.pose_f64 = c.take<double>(hyps * 12);
-    o.cws = c.take<double>(hyps * 12);
-    o.ut_tail = c.take<double>(hyps * 48);
-    o.betas = c.take<double>(hyps * 12);
-    o.rep_errors = c.take<double>(hyps * 3);
-    o.pca = c.take<double>(hyps * 9);
-    o.rec_pose_f64 = c.take<double>(recs * 12);
-    o.rec_cws = c.take<double>(recs * 12);
-    o.rec_ut_tail = c.take<double>(recs * 48);
-    o.rec_betas = c.take<double>(recs * 12);
-    o.rec_rep_errors = c.take<double>(recs * 3);
-    o.rec_pca = c.take<double>(recs * 9);
-  });
-}
 
 // nullptr when params and out are usable, else what is wrong with them
 const char* pnp_fault(const msf_pnp_params* prm, const msf_pnp_result* out) {
@@ -1375,8 +1337,17 @@ int msf_pnp_ransac(msf_handle* h, int32_t n, const float* p3d, const float* p2d,
     CallScope cs{h};
     if (int rc = cs.enter()) return rc;
     const size_t cap = n > 0 ? (size_t)n : 1, its = (size_t)params->n_iterations;
+    const size_t units[] = {1, its, (size_t)params->max_records};
+    msf_pnp_result want = *out, dev{};
+    if (sets) want.sets = nullptr;   // the sets come back only when they were drawn here
     PnpPlan p;
-    if (int rc = plan_pnp(h, 1, cap, params, nullptr, sets != nullptr, &p)) return rc;
+    if (int rc = carve(h, h->d_pnp, (size_t)1 << 16, "hipMalloc(pnp workspace)", [&](msf::Carver& c) {
+          p.p3d = c.take<float>(cap * 3);
+          p.p2d = c.take<float>(cap * 2);
+          p.sets_in = sets ? c.take<int32_t>(its * 4) : nullptr;
+          msf::carve_result(c, msf::kPnpArrays, units, cap, nullptr, want, &dev);
+        }))
+      return rc;
     hipStream_t st = cs.st;
     Drain drain{st};
     if (n > 0) {
@@ -1385,38 +1356,15 @@ int msf_pnp_ransac(msf_handle* h, int32_t n, const float* p3d, const float* p2d,
     }
     if (sets) HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.sets_in, sets, its * 16, hipMemcpyHostToDevice, st));
     const msf::PnpLists in{p.p3d, p.p2d, (int32_t)cap, nullptr, n, p.sets_in};
-    HIP_TRY(h, "pnp_ransac", msf::pnp_ransac(1, in, pnp_params(params), p.out, st));
-    if (int rc = fetch(h, st, out->n_records, p.out.n_records, 4)) return rc;
+    HIP_TRY(h, "pnp_ransac", msf::pnp_ransac(1, in, pnp_params(params), to_out(dev), st));
+    if (int rc = fetch(h, st, out->n_records, dev.n_records, sizeof *out->n_records)) return rc;
     HIP_TRY(h, "hipStreamSynchronize", hipStreamSynchronize(st));   // the count decides what else there is to copy
     const int32_t records = out->n_records[0];
     if (records >= 0) {
-      const msf::PnpOut& d = p.out;
-      if (int rc = fetch(h, st, out->counts, d.counts, its * 4)) return rc;
-      if (!sets)
-        if (int rc = fetch(h, st, out->sets, d.sets, its * 16)) return rc;
-      if (int rc = fetch(h, st, out->pose_f64, d.pose_f64, its * 96)) return rc;
-      if (int rc = fetch(h, st, out->cws, d.cws, its * 96)) return rc;
-      if (int rc = fetch(h, st, out->ut_tail, d.ut_tail, its * 384)) return rc;
-      if (int rc = fetch(h, st, out->betas, d.betas, its * 96)) return rc;
-      if (int rc = fetch(h, st, out->rep_errors, d.rep_errors, its * 24)) return rc;
-      if (int rc = fetch(h, st, out->pca, d.pca, its * 72)) return rc;
-      const size_t k = (size_t)(records < params->max_records ? records : params->max_records);
-      if (int rc = fetch(h, st, out->iteration, d.iteration, k * 4)) return rc;
-      if (int rc = fetch(h, st, out->n_inliers, d.n_inliers, k * 4)) return rc;
-      if (int rc = fetch(h, st, out->refined_ok, d.refined_ok, k * 4)) return rc;
-      if (int rc = fetch(h, st, out->n_refined, d.n_refined, k * 4)) return rc;
-      if (int rc = fetch(h, st, out->Tcw_best, d.tcw_best, k * 48)) return rc;
-      if (int rc = fetch(h, st, out->Tcw_refined, d.tcw_refined, k * 48)) return rc;
-      if (int rc = fetch(h, st, out->rec_pose_f64, d.rec_pose_f64, k * 96)) return rc;
-      if (int rc = fetch(h, st, out->rec_cws, d.rec_cws, k * 96)) return rc;
-      if (int rc = fetch(h, st, out->rec_ut_tail, d.rec_ut_tail, k * 384)) return rc;
-      if (int rc = fetch(h, st, out->rec_betas, d.rec_betas, k * 96)) return rc;
-      if (int rc = fetch(h, st, out->rec_rep_errors, d.rec_rep_errors, k * 24)) return rc;
-      if (int rc = fetch(h, st, out->rec_pca, d.rec_pca, k * 72)) return rc;
-      for (size_t rec = 0; rec < k; rec++) {   // a row ends with the list
-        if (int rc = fetch(h, st, from(out->inliers_best, rec * cap), d.inliers_best + rec * cap, (size_t)n)) return rc;
-        if (int rc = fetch(h, st, from(out->inliers_refined, rec * cap), d.inliers_refined + rec * cap, (size_t)n)) return rc;
-      }
+      want.n_records = nullptr;   // has arrived
+      const size_t rows[] = {1, its, (size_t)(records < params->max_records ? records : params->max_records)};
+      const msf::Extent e{0, cap, cap, (size_t)n, units, rows};   // an inlier row ends with the list
+      if (int rc = fetch_result(h, st, msf::kPnpArrays, dev, want, e)) return rc;
     }
     drain.armed = false;
     if (int rc = cs.finish()) return rc;
@@ -1441,19 +1389,24 @@ int msf_pnp_ransac_device(msf_handle* h, int32_t n_lists, const float* d_p3d, co
     if (n_lists == 0) return MSF_OK;
     CallScope cs{h};
     if (int rc = cs.enter(stream)) return rc;
-    PnpPlan p;
-    if (int rc = plan_pnp(h, (size_t)n_lists, (size_t)cap, params, out, false, &p)) return rc;
+    // the counts and poses that the second launch reads get a piece when the caller does not ask for them
+    const size_t units[] = {(size_t)n_lists, (size_t)params->n_iterations, (size_t)params->max_records};
+    msf_pnp_result dev{};
+    if (int rc = carve(h, h->d_pnp, (size_t)1 << 16, "hipMalloc(pnp workspace)", [&](msf::Carver& c) {
+          msf::carve_result(c, msf::kPnpArrays, units, (size_t)cap, out, *out, &dev);
+        }))
+      return rc;
     const msf::PnpLists in{d_p3d, d_p2d, cap, d_n, 0, d_sets};
-    HIP_TRY(h, "pnp_ransac", msf::pnp_ransac(n_lists, in, pnp_params(params), p.out, cs.st));
+    HIP_TRY(h, "pnp_ransac", msf::pnp_ransac(n_lists, in, pnp_params(params), to_out(dev), cs.st));
     return cs.finish();
   });
 }
 
 namespace {
 
-// Where msf_pose_optimize keeps its device data: the list, and a piece for every result the caller asked for.
+// What msf_pose_optimize keeps in the workspace besides its result arrays (result_arrays.h: kPoseArrays): the list,
+// its entry pose and mask; base / bytes: the whole of it, for the memset.
 struct PosePlan {
-  msf::PoseOut out{};
   float* p3d = nullptr;
   float* p2d = nullptr;
   float* tcw0 = nullptr;
@@ -1461,36 +1414,6 @@ struct PosePlan {
   size_t bytes = 0;
   uint8_t* base = nullptr;
 };
-
-int plan_pose(msf_handle* h, size_t cap, bool with_mask, const msf_pose_result* want, PosePlan* p) {
-  constexpr size_t R = 4, I = 40;
-  return carve(h, h->d_pose, (size_t)1 << 16, "hipMalloc(pose workspace)", [&](msf::Carver& c) {
-    msf::PoseOut& o = p->out;
-    p->base = c.base;
-    p->p3d = c.take<float>(cap * 3);
-    p->p2d = c.take<float>(cap * 2);
-    p->tcw0 = c.take<float>(12);
-    p->mask = with_mask ? c.take<uint8_t>(cap) : nullptr;
-    o.n_good = c.take<int32_t>(1);
-    o.tcw = want->Tcw ? c.take<float>(12) : nullptr;
-    o.outliers = want->outliers ? c.take<uint8_t>(cap) : nullptr;
-    o.n_edges = want->n_edges ? c.take<int32_t>(1) : nullptr;
-    o.rounds_run = want->rounds_run ? c.take<int32_t>(1) : nullptr;
-    o.pose_f64 = want->pose_f64 ? c.take<double>(12) : nullptr;
-    o.round_pose_f64 = want->round_pose_f64 ? c.take<double>(R * 12) : nullptr;
-    o.round_n_bad = want->round_n_bad ? c.take<int32_t>(R) : nullptr;
-    o.round_iterations = want->round_iterations ? c.take<int32_t>(R) : nullptr;
-    o.it_trials = want->it_trials ? c.take<int32_t>(I) : nullptr;
-    o.it_lambda_in = want->it_lambda_in ? c.take<double>(I) : nullptr;
-    o.it_lambda_out = want->it_lambda_out ? c.take<double>(I) : nullptr;
-    o.it_cost_in = want->it_cost_in ? c.take<double>(I) : nullptr;
-    o.it_cost_out = want->it_cost_out ? c.take<double>(I) : nullptr;
-    o.it_H = want->it_H ? c.take<double>(I * 21) : nullptr;
-    o.it_b = want->it_b ? c.take<double>(I * 6) : nullptr;
-    o.it_pose_out = want->it_pose_out ? c.take<double>(I * 7) : nullptr;
-    p->bytes = c.off;
-  });
-}
 
 // nullptr when params and out are usable, else what is wrong with them
 const char* pose_fault(const msf_pose_params* prm, const msf_pose_result* out) {
@@ -1514,8 +1437,19 @@ int msf_pose_optimize(msf_handle* h, int32_t n, const float* p3d, const float* p
     CallScope cs{h};
     if (int rc = cs.enter()) return rc;
     const size_t cap = n > 0 ? (size_t)n : 1, count = (size_t)n;
+    const size_t units[] = {1, msf::kPoseRounds, msf::kPoseIterations};
+    msf_pose_result dev{};
     PosePlan p;
-    if (int rc = plan_pose(h, cap, mask != nullptr, out, &p)) return rc;
+    if (int rc = carve(h, h->d_pose, (size_t)1 << 16, "hipMalloc(pose workspace)", [&](msf::Carver& c) {
+          p.base = c.base;
+          p.p3d = c.take<float>(cap * 3);
+          p.p2d = c.take<float>(cap * 2);
+          p.tcw0 = c.take<float>(12);
+          p.mask = mask ? c.take<uint8_t>(cap) : nullptr;
+          msf::carve_result(c, msf::kPoseArrays, units, cap, nullptr, *out, &dev);
+          p.bytes = c.off;
+        }))
+      return rc;
     hipStream_t st = cs.st;
     Drain drain{st};
     // what the kernel leaves alone comes back as 0, and an outlier byte outside the mask as the caller had it
@@ -1525,30 +1459,14 @@ int msf_pose_optimize(msf_handle* h, int32_t n, const float* p3d, const float* p
       HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.p2d, p2d, count * 8, hipMemcpyHostToDevice, st));
       if (mask) HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.mask, mask, count, hipMemcpyHostToDevice, st));
       if (mask && out->outliers)
-        HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.out.outliers, out->outliers, count, hipMemcpyHostToDevice, st));
+        HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(dev.outliers, out->outliers, count, hipMemcpyHostToDevice, st));
     }
     HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.tcw0, Tcw0, 48, hipMemcpyHostToDevice, st));
     const msf::PoseLists in{p.p3d, p.p2d, (int32_t)cap, nullptr, n, p.tcw0, 0, p.mask, 0};
     const msf::PoseParams prm{params->fx, params->fy, params->cx, params->cy, params->chi2};
-    HIP_TRY(h, "pose_optimize", msf::pose_optimize(1, in, prm, p.out, st));
-    const msf::PoseOut& d = p.out;
-    if (int rc = fetch(h, st, out->n_good, d.n_good, 4)) return rc;
-    if (int rc = fetch(h, st, out->Tcw, d.tcw, 48)) return rc;
-    if (int rc = fetch(h, st, out->outliers, d.outliers, count)) return rc;
-    if (int rc = fetch(h, st, out->n_edges, d.n_edges, 4)) return rc;
-    if (int rc = fetch(h, st, out->rounds_run, d.rounds_run, 4)) return rc;
-    if (int rc = fetch(h, st, out->pose_f64, d.pose_f64, 96)) return rc;
-    if (int rc = fetch(h, st, out->round_pose_f64, d.round_pose_f64, 4 * 96)) return rc;
-    if (int rc = fetch(h, st, out->round_n_bad, d.round_n_bad, 16)) return rc;
-    if (int rc = fetch(h, st, out->round_iterations, d.round_iterations, 16)) return rc;
-    if (int rc = fetch(h, st, out->it_trials, d.it_trials, 40 * 4)) return rc;
-    if (int rc = fetch(h, st, out->it_lambda_in, d.it_lambda_in, 40 * 8)) return rc;
-    if (int rc = fetch(h, st, out->it_lambda_out, d.it_lambda_out, 40 * 8)) return rc;
-    if (int rc = fetch(h, st, out->it_cost_in, d.it_cost_in, 40 * 8)) return rc;
-    if (int rc = fetch(h, st, out->it_cost_out, d.it_cost_out, 40 * 8)) return rc;
-    if (int rc = fetch(h, st, out->it_H, d.it_H, 40 * 21 * 8)) return rc;
-    if (int rc = fetch(h, st, out->it_b, d.it_b, 40 * 6 * 8)) return rc;
-    if (int rc = fetch(h, st, out->it_pose_out, d.it_pose_out, 40 * 7 * 8)) return rc;
+    HIP_TRY(h, "pose_optimize", msf::pose_optimize(1, in, prm, to_out(dev), st));
+    const msf::Extent all{0, cap, cap, count, units, units};
+    if (int rc = fetch_result(h, st, msf::kPoseArrays, dev, *out, all)) return rc;
     drain.armed = false;
     return cs.finish();
   });
@@ -1570,11 +1488,7 @@ int msf_pose_optimize_device(msf_handle* h, int32_t n_lists, const float* d_p3d,
     if (int rc = cs.enter(stream)) return rc;
     const msf::PoseLists in{d_p3d, d_p2d, cap, d_n, 0, d_Tcw0, Tcw0_stride, d_mask, mask_stride};
     const msf::PoseParams prm{params->fx, params->fy, params->cx, params->cy, params->chi2};
-    const msf::PoseOut o{out->n_good, out->Tcw, out->outliers, out->n_edges, out->rounds_run, out->pose_f64,
-                         out->round_pose_f64, out->round_n_bad, out->round_iterations, out->it_trials,
-                         out->it_lambda_in, out->it_lambda_out, out->it_cost_in, out->it_cost_out, out->it_H, out->it_b,
-                         out->it_pose_out};
-    HIP_TRY(h, "pose_optimize", msf::pose_optimize(n_lists, in, prm, o, cs.st));
+    HIP_TRY(h, "pose_optimize", msf::pose_optimize(n_lists, in, prm, to_out(*out), cs.st));
     return cs.finish();
   });
 }
