@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "carve.h"
+#include "dev_buf.h"
 #include "loftr_pipeline.h"
 #include "msf_initializer.h"
 #include "msf_local_mapping.h"
@@ -48,31 +49,7 @@ hipError_t ransac_sets(int n_lists, int n_hyp, const int32_t* d_n_out, int cap, 
 
 namespace {
 thread_local std::string g_create_error;
-
-// Owning device allocation: a pointer and its size in bytes; reads as the pointer, freed with the handle.
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t bytes = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
-  operator T*() const { return p; }
-  void release() {
-    if (p) hipFree(p);   // waits for the device: no earlier call still uses the block
-    p = nullptr;
-    bytes = 0;
-  }
-  // Drops the old block, then allocates max(want, floor) bytes; empty after a failure.
-  hipError_t reserve(size_t want, size_t floor = 0) {
-    release();
-    const size_t n = want > floor ? want : floor;
-    const hipError_t e = hipMalloc(&p, n);
-    if (e != hipSuccess) p = nullptr; else bytes = n;
-    return e;
-  }
-};
+using msf::DevBuf;   // dev_buf.h: the handle's device blocks go with their members
 }  // namespace
 
 struct msf_handle {
@@ -585,10 +562,18 @@ int msf_create(const msf_config* cfg, msf_handle** out) {
     }
     if (cfg->kind == MSF_KIND_ORB) {
       h->fc_slot0 = 4 * cfg->max_batch_pairs;
-      err = h->orb.init(cfg->image_width, cfg->image_height, 4 * cfg->max_batch_pairs + n_cache,
-                        (cfg->flags & MSF_FLAG_BLUR_TIE_HALF_UP) != 0, profile, (cfg->flags & MSF_FLAG_FAST_DENSE) != 0,
-                        (cfg->flags & MSF_FLAG_LEVEL_SIZE_MUL_INV) != 0, (cfg->flags & MSF_FLAG_FAST_STREAM) ? 1 : 8,
-                        (cfg->flags & MSF_FLAG_BLUR_SUM256) != 0, 2 * cfg->max_batch_pairs);
+      msf::OrbOptions o;
+      o.width = cfg->image_width;
+      o.height = cfg->image_height;
+      o.max_slots = 4 * cfg->max_batch_pairs + n_cache;
+      o.work_frames = 2 * cfg->max_batch_pairs;
+      o.blur_half_up = (cfg->flags & MSF_FLAG_BLUR_TIE_HALF_UP) != 0;
+      o.blur_sum256 = (cfg->flags & MSF_FLAG_BLUR_SUM256) != 0;
+      o.profile = profile;
+      o.dense_fast = (cfg->flags & MSF_FLAG_FAST_DENSE) != 0;
+      o.level_size_mul_inv = (cfg->flags & MSF_FLAG_LEVEL_SIZE_MUL_INV) != 0;
+      o.stream_min_frames = (cfg->flags & MSF_FLAG_FAST_STREAM) ? 1 : 8;
+      err = h->orb.init(o);
     } else {
       if (cfg->image_width != 640 || cfg->image_height != 480)
         return fail(nullptr, MSF_ERR_UNSUPPORTED, "LoFTR_teacher is a fixed-shape 1x1x480x640 graph (model/LoFTR_teacher.onnx)");

@@ -19,21 +19,15 @@
 
 namespace msf {
 
-// ------------------------------------------------------------------ constants
-constexpr int kEdge = 31;          // edgeThreshold
-constexpr int kFastT = 20;         // fastThreshold
-constexpr int TW = 128, TH = 32;    // FAST output tile
+// ------------------------------------------------------------------ constants (those the level plan shares: orb_plan.h)
 constexpr int SW = TW + 2, SH = TH + 2;    // scored region: tile + 1 halo (NMS neighbours)
 constexpr int kTileCandCap = TW * TH / 4;    // strict 3x3 maxima: at most one per 2x2
-constexpr int kTileX0 = 16, kTileY0 = kEdge;  // tile grid origin: first output column 31 rounded down to the 16-byte load grid
+constexpr int kTileY0 = kEdge;               // tile grid origin (kTileX0: orb_plan.h)
 
 constexpr uint32_t kStatusOverflow = 1u;
 
 __constant__ __attribute__((aligned(16))) signed char c_pattern[1024];
-// ICAngles disc as 31 rows x 8 dwords of 4 pixels (u = -16 + 4k .. -13 + 4k): per dword the signed byte weights u
-// (0 outside the disc) and the signed byte weights v (the row's, 0 outside the disc), padded to 4 x 64 tasks
-constexpr int kDiscTasks = 256;
-__constant__ uint32_t c_disc[2 * kDiscTasks];
+__constant__ uint32_t c_disc[2 * kDiscTasks];   // OrbPlan::disc
 
 // ------------------------------------------------------------------ helpers
 // a pointer / integer the caller knows to be the same in every lane, pinned to scalar registers.  A buffer descriptor
@@ -556,16 +550,7 @@ constexpr int kQDone = kTauBins, kQTau = kTauBins + 1, kQFirst = kTauBins + 2, k
 constexpr int kQStat = kTauBins + 4;
 constexpr uint32_t kQReady = 0x80000000u;
 constexpr int RK = 16;                   // ring rows (power of two)
-constexpr int kWkMaxPx = 244;            // strip pitch <= 244: a group of 4 output px reads two aligned 8-byte pairs <= 8 B apart
-constexpr int kWkMaxRows = 240;          // owned rows per strip at most (a strip's emit table lives in four registers per lane)
-// Owned rows per strip aimed at.  With the levels as separate launches 80 rows measured best (r03: 48 / 64 / 80 / 96 / 112
-// rows 8.19 / 7.97 / 7.83 / 7.88 / 7.96 ms per 720p step: taller strips lengthen every launch's tail).  In the one-launch
-// form there is one tail, and what counts is the work a strip repeats -- 8 halo rows, its prologue, its drain:
-// 64 / 80 / 112 / 144 / 180 / 240 rows measured 5.47 / 5.24 / 4.97 / 4.86 / 4.78 / 4.79 ms for the stage at 1280 x 720
-// (1024 pairs) and 9.92 (80) / 9.45 (112) / 8.80 (144) / 8.62 (240) ms at 640 x 480 (4096 pairs).  Handles for small
-// batches keep short strips: their calls are latency-bound chains of (quarter, rest) x 8 levels.
-constexpr int kWkRowsTall = 240, kWkRowsShort = 80, kWkTallMinSlots = 4 * 64;
-constexpr int kTauSites = 1024;          // sampled runs of 4 px per (frame, level) of the threshold sampler (512 / 2048 / 4096: slower)
+// (kWkMaxPx, kWkMaxRows, the strip heights and kTauSites: orb_plan.h)
 constexpr int kSGCap = 288, kSPCap = 256, kSHCap = 64, kSOCap = 64;   // 10 240 B of LDS per wave: exactly 16 waves per CU
 constexpr uint32_t kSGFlush = 32;        // records that trigger a flush at the end of a four-step group (<= 4 x 64 more arrive)
 static_assert(kSGCap >= (int)kSGFlush + 256, "record list capacity");
@@ -633,10 +618,7 @@ __device__ __forceinline__ int stream_score(const uint8_t* ring, uint32_t r0, ui
 // on the reading side; thresholds may differ from run to run in principle, the candidate lists they lead to contain
 // every corner retainBest(2N) can keep either way (k_fast_check).
 constexpr uint32_t kSpinMax = 1u << 19;
-// A vector offset no level the walker makes reaches (host-checked: such a level is below 1 GB): the buffer range check
-// drops a store at it, whatever row offset comes on top.  dxoff | kRzNoStore stays in [1 GB, 2 GB).
-constexpr uint32_t kRzNoStore = 0x40000000u;
-
+// (kRzNoStore, the vector offset at which the buffer range check drops a store: orb_plan.h)
 
 __device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1752,11 +1734,7 @@ __global__ __launch_bounds__(256) void k_thr_harris(OrbGeometry g, FrameSrc src,
 // hw.n[l] units (enough for 2N x 1.25 entries: retainBest(2N) keeps 2N plus the ties of the last score; a longer list is
 // walked in steps of hw.n[l] x 64), one wave per unit.  k_thr_harris with one wave per (frame, level) spent four fifths
 // of its time here -- level 0 alone is four dependent rounds of 27 scattered loads at 4 waves per SIMD -- 0.39 ms of the
-// 0.56 ms selection stage per 2048 720p frames.
-struct HarrisUnits {
-  int base[kOrbLevels + 1];    // first unit of level l; base[nlevels] = units per frame
-  int n[kOrbLevels];
-};
+// 0.56 ms selection stage per 2048 720p frames.  (HarrisUnits: orb_plan.h)
 __global__ __launch_bounds__(256) void k_harris_flat(OrbGeometry g, FrameSrc src, const uint8_t* pyr, HarrisUnits hw,
                                                      const uint32_t* __restrict__ s1_cnt, uint4* s1) {
   const int fi = blockIdx.y, slot = src.slot0 + fi, lane = threadIdx.x & 63;
@@ -2325,42 +2303,16 @@ __global__ __launch_bounds__(256) void k_match_split(int n_pairs, const int32_t*
 }
 
 // ================================================================== host side
-static int cv_round_f(float v) { return (int)lrintf(v); }
-static int cv_round_d(double v) { return (int)lrint(v); }
-
-// interpolationLinear<uchar>::getCoeffs (imgproc resize.cpp, INTER_LINEAR_EXACT)
-static void make_table(int src, int dst, uint32_t* tab) {
-  const double inv_scale = (double)dst / (double)src;
-  const double scale = 1.0 / inv_scale;
-  for (int d = 0; d < dst; d++) {
-    const double f = scale * ((double)d + 0.5) - 0.5;
-    const int i = (int)floor(f);
-    if (i >= 0 && src > 1) {
-      if (i < src - 1) {
-        tab[d] = (uint32_t)i | ((uint32_t)cv_round_d((f - (double)i) * 256.0) << 16);
-      } else {
-        tab[d] = (uint32_t)(src - 1);   // replicate the last pixel: weight 0 on the (absent) right/bottom tap
-      }
-    } else {
-      tab[d] = 0;                       // replicate the first pixel
-    }
-  }
-}
-
 OrbPipeline::~OrbPipeline() { destroy(); }
 
 void OrbPipeline::destroy() {
-  hipFree(d_tau_); hipFree(d_redo_); hipFree(d_qstat_); hipFree(d_walk_abort_);
   if (h_walk_abort_) hipHostFree(h_walk_abort_);
-  d_tau_ = nullptr; d_redo_ = nullptr; d_qstat_ = nullptr; d_walk_abort_ = nullptr; h_walk_abort_ = nullptr;
-  hipFree(d_pyr_); hipFree(d_tab_); hipFree(d_cand_cnt_); hipFree(d_cand_); hipFree(d_cand_sc_); hipFree(d_cmap_); hipFree(d_redo_hist_); hipFree(d_redo_thr_); hipFree(d_qres_); hipFree(d_done_); hipFree(d_s1_cnt_); hipFree(d_s1_);
-  hipFree(d_kp_); hipFree(d_desc_); hipFree(d_kp_cnt_); hipFree(d_status_);
-  d_pyr_ = nullptr; d_tab_ = nullptr; d_cand_cnt_ = nullptr; d_cand_ = nullptr; d_cand_sc_ = nullptr; d_cmap_ = nullptr; d_redo_hist_ = nullptr; d_redo_thr_ = nullptr; d_qres_ = nullptr; d_done_ = nullptr; d_s1_cnt_ = nullptr;
-  d_s1_ = nullptr; d_kp_ = nullptr; d_desc_ = nullptr; d_kp_cnt_ = nullptr; d_status_ = nullptr;
-  if (ev_ok_) {
-    for (auto& set : evr_)
-      for (auto& e : set.ev) if (e) hipEventDestroy(e);
-  }
+  h_walk_abort_ = nullptr;
+  for (auto& set : evr_)
+    for (auto& e : set.ev) {
+      if (e) hipEventDestroy(e);   // (those of an init that failed half way too)
+      e = nullptr;
+    }
   ev_ok_ = false;
 }
 
@@ -2370,21 +2322,9 @@ void OrbPipeline::destroy() {
     if (e_ != hipSuccess) return std::string(#expr) + ": " + hipGetErrorString(e_);       \
   } while (0)
 
-std::string OrbPipeline::init(int width, int height, int max_slots, bool blur_half_up, bool profile, bool dense_fast,
-                              bool level_size_mul_inv, int stream_min_frames, bool blur_sum256, int work_frames) {
-  if (width < 64 || height < 64 || width > 8192 || height > 8192) return "arg: ORB image size must be in [64, 8192] x [64, 8192]";
-  if (max_slots < 2) return "arg: ORB max_slots < 2";
-  max_slots_ = max_slots;
-  // frames one extraction may hold: the pyramid, the candidate and stage-1 lists and the walker's state exist once per
-  // frame of a CALL (work rows), only key points and descriptors once per feature slot
-  work_frames_ = work_frames <= 0 || work_frames > max_slots ? max_slots : work_frames < 2 ? 2 : work_frames;
-  half_up_ = blur_half_up;
-  blur_sum256_ = blur_sum256;
-  profile_ = profile;
+void OrbPipeline::read_env() {
   // MSF_ORB_FAST_TAU forces the first-pass FAST threshold (tests: a value no level can reach sends every level through
   // the check + dense second pass); MSF_FLAG_FAST_DENSE = 20 = the plain dense detector
-  force_tau_ = dense_fast ? kFastT : 0;
-  stream_min_frames_ = stream_min_frames;
   if (const char* e = getenv("MSF_ORB_FAST_TAU")) {
     const int v = atoi(e) & ~1;
     if (v >= kFastT && v <= 254) force_tau_ = v;
@@ -2395,7 +2335,7 @@ std::string OrbPipeline::init(int width, int height, int max_slots, bool blur_ha
   // MSF_ORB_FAST_ONE_PART=1: the streaming FAST pass over all strips at the first threshold (no prediction, no refinement)
   if (const char* e = getenv("MSF_ORB_FAST_ONE_PART")) fast_two_part_ = atoi(e) == 0;
   // MSF_ORB_UNFUSED=1: the pyramid by k_resize and one FAST-only walker launch over all levels (the fallback for level
-  // geometries whose tables fail the host checks below; tests compare it with the fused default, in which the walker of
+  // geometries whose tables fail the checks of plan_orb; tests compare it with the fused default, in which the walker of
   // level l - 1 also makes level l)
   if (const char* e = getenv("MSF_ORB_UNFUSED")) fused_ = atoi(e) == 0;
   if (getenv("MSF_TEST_HOOKS"))
@@ -2416,255 +2356,74 @@ std::string OrbPipeline::init(int width, int height, int max_slots, bool blur_ha
     const int v = atoi(e);
     if (v >= 1 && v <= 10000) tau2_margin_pct_ = v;
   }
-  OrbGeometry& g = g_;
-  g.nlevels = kOrbLevels;
-  g.w0 = width;
-  g.h0 = height;
-  // ORB_Impl::detectAndCompute: layer scales and sizes; computeKeyPoints: per-level quotas and umax
-  const float scale_factor_f = 1.2f;
-  const double scale_factor = (double)scale_factor_f;
-  const int nfeatures = 500;
-  {
-    const float factor = (float)(1.0 / scale_factor);
-    float nd = (float)nfeatures * (1 - factor) / (1 - (float)pow((double)factor, (double)g.nlevels));
-    int sum = 0;
-    for (int l = 0; l < g.nlevels - 1; l++) {
-      g.lv[l].quota = cv_round_f(nd);
-      sum += g.lv[l].quota;
-      nd *= factor;
-    }
-    g.lv[g.nlevels - 1].quota = nfeatures - sum > 0 ? nfeatures - sum : 0;
-  }
-  {
-    const int half = 15;
-    int umax[17] = {0};
-    const int vmax = (int)floor(half * sqrt(2.f) / 2 + 1);
-    const int vmin = (int)ceil(half * sqrt(2.f) / 2);
-    for (int v = 0; v <= vmax; ++v) umax[v] = cv_round_d(sqrt((double)half * half - v * v));
-    for (int v = half, v0 = 0; v >= vmin; --v) {
-      while (umax[v0] == umax[v0 + 1]) ++v0;
-      umax[v] = v0;
-      ++v0;
-    }
-    for (int v = 0; v < 16; v++) g.umax[v] = umax[v];
-  }
-  long long pix = 0;
-  int cand = 0, prim = 0, tiles = 0, strips = 0, tab = 0, s1 = 0;
-  g.max_level_tiles = 0;
-  for (int l = 0; l < g.nlevels; l++) {
-    OrbLevelInfo& L = g.lv[l];
-    const float s = (float)pow(scale_factor, (double)l);
-    const float inv = 1.0f / s;
-    L.scale = s;
-    // ORB_Impl::detectAndCompute (OpenCV 3.x / 4.x): Size sz(cvRound(image.cols/scale), cvRound(image.rows/scale));
-    // MSF_FLAG_LEVEL_SIZE_MUL_INV selects the 2.4-era cvRound(cols * (1.f / scale)) instead (they differ for a few odd
-    // sizes, e.g. width 69 -> 57 vs 58 at level 1; never for 640 / 480 / 1280 / 720 / 1920 / 1080)
-    L.w = level_size_mul_inv ? cv_round_f((float)width * inv) : cv_round_f((float)width / s);
-    L.h = level_size_mul_inv ? cv_round_f((float)height * inv) : cv_round_f((float)height / s);
-    L.pitch = (L.w + 15) & ~15;
-    L.pix_off = pix;
-    if (l > 0) pix += (long long)L.pitch * L.h;
-    // strict 3x3 maxima are at most w*h/4; w*h/8 covers white noise with margin (overflow is flagged, never silent)
-    int cap = (int)((long long)L.w * L.h / 8);
-    if (cap < 4096) cap = 4096;
-    cap = (cap + 15) & ~15;   // score bytes of a level start 16-byte aligned
-    L.cand_cap = cap;
-    L.cand_off = cand;
-    cand += cap;
-    // the output-sensitive pass lists the maxima at or above the level's threshold -- about a thousand at 1280 x 720
-    // against ~20 000 maxima in all --: the primary list is an eighth of the full one (a list that overflows all the same
-    // sends its level to the dense pass, k_fast_check), and at least kS1Cap: the dense pass lists the level's stage 1
-    // into it, so every stage 1 that fits kS1Cap fits its primary list
-    int pcap = (int)((long long)L.w * L.h / 64);
-    if (pcap < kS1Cap) pcap = kS1Cap;
-    pcap = (pcap + 15) & ~15;
-    // small levels keep their full capacity (little memory, and small levels are the ones that take the dense pass:
-    // their thresholds rest on few corners): only lists above 16 K entries are cut
-    if (pcap > cap || cap <= 16384) pcap = cap;
-    prim_.cap[l] = pcap;
-    prim_.off[l] = prim;
-    prim += pcap;
-    L.s1_off = s1;
-    s1 += kS1Cap;
-    // FAST tiles cover only the pixels runByImageBorder(31) can keep, [31, w-31) x [31, h-31) (17 % fewer tiles on
-    // the 720p pyramid than tiling the whole level); levels without such pixels get no tiles
-    L.tiles_x = L.w > 2 * kEdge ? (L.w - kEdge - kTileX0 + TW - 1) / TW : 0;
-    L.tiles_y = L.h > 2 * kEdge ? (L.h - 2 * kEdge + TH - 1) / TH : 0;
-    if (L.tiles_x == 0 || L.tiles_y == 0) L.tiles_x = L.tiles_y = 0;
-    L.tile_base = tiles;
-    tiles += L.tiles_x * L.tiles_y;
-    // walker strips over the whole level: 256-px windows wk_px apart ((nx - 1) * wk_px + 256 >= w), wk_rows owned rows
-    L.wk_nx = L.w > 256 ? (L.w - 256 + kWkMaxPx - 1) / kWkMaxPx + 1 : 1;
-    L.wk_px = L.wk_nx > 1 ? (((L.w - 256 + L.wk_nx - 2) / (L.wk_nx - 1)) + 3) & ~3 : kWkMaxPx;
-    const int rows_target = max_slots >= kWkTallMinSlots ? kWkRowsTall : kWkRowsShort;
-    L.wk_ny = (L.h + rows_target - 1) / rows_target;
-    L.wk_rows = (((L.h + L.wk_ny - 1) / L.wk_ny) + 3) & ~3;
-    L.wk_ny = (L.h + L.wk_rows - 1) / L.wk_rows;
-    L.wk_base = strips;
-    strips += L.wk_nx * L.wk_ny;
-    L.wk_fused = 0;
-    L.tab_yemit = L.tab_xstrip = 0;
-    if (L.tiles_x * L.tiles_y > g.max_level_tiles) g.max_level_tiles = L.tiles_x * L.tiles_y;
-    // sample lattice of tau_unit: about 4096 pixels of the kept region in runs of 4 (one dword), rows sparser than
-    // columns (a sampled pixel touches 7 rows); samp_sx counts dwords and is odd, so that block textures with
-    // power-of-two periods are not aliased
-    L.samp_sx = L.samp_sy = 1;
-    L.samp_rows = L.samp_cols = 0;
-    if (L.tiles_x > 0) {
-      const int rh = L.h - 2 * kEdge;
-      const int n_dw = (L.w - kEdge - ((kEdge + 3) & ~3)) >> 2;          // aligned dwords fully inside [31, w - 31)
-      const double s2 = (double)n_dw * rh / (double)kTauSites;          // (dword, row) sites per sampled run
-      int sx = (int)(sqrt(s2 > 1.0 ? s2 : 1.0) / 4.0);
-      sx = (sx < 1 ? 1 : sx) | 1;
-      int sy = (int)(s2 / sx + 0.5);
-      sy = sy < 1 ? 1 : sy;
-      L.samp_sx = sx;
-      L.samp_sy = sy;
-      L.samp_rows = (rh + sy - 1) / sy;
-      L.samp_cols = n_dw > 0 ? (n_dw + sx - 1) / sx : 0;
-      if (L.samp_cols == 0) L.samp_rows = 0;
-    }
-    L.tab_off = tab;
-    if (l > 0) {
-      tab += 12 * ((L.w + 3) >> 2) + ((L.h + 3) & ~3);   // 3 x uint4 per group of 4 columns, one dword per row
-      L.tab_yemit = tab;                                 // one dword per SOURCE row (level l - 1)
-      tab += (g.lv[l - 1].h + 3) & ~3;
-      L.tab_xstrip = tab;                                // first output group of each walker strip of level l - 1, + end
-      tab += (g.lv[l - 1].wk_nx + 1 + 3) & ~3;
-    }
-  }
-  g.pyr_bytes = (pix + 255) & ~255ll;
-  g.cand_total = cand;
-  g.prim_total = prim;
-  g.s1_total = s1;
-  g.total_tiles = tiles;
-  g.total_strips = strips;
+}
 
-  std::vector<uint32_t> htab(tab > 0 ? tab : 1, 0u);
-  for (int l = 1; l < g.nlevels; l++) {
-    const OrbLevelInfo& L = g.lv[l];
-    const int groups = (L.w + 3) >> 2;
-    std::vector<uint32_t> xt(4 * groups);
-    make_table(g.lv[l - 1].w, L.w, xt.data());
-    for (int x = L.w; x < 4 * groups; x++) xt[x] = xt[L.w - 1];   // pad entries: the last pixel again
-    // k_resize<true> reads pixels 4g .. 4g+2 from the dword pair of pixel 4g: needs tap offset (rel. to that pair) <= 6
-    bool shared = !resize_generic_;
-    for (int x = 0; x < 4 * groups; x += 4)
-      for (int k = 1; k < 3; k++)
-        if ((xt[x + k] & 0xFFFFu) - (xt[x] & 0xFFFCu) > 6u) shared = false;
-    resize_shared_[l] = shared;
-    uint32_t* xsel = htab.data() + L.tab_off;
-    uint32_t* xwxp = xsel + 4 * groups;
-    uint32_t* xoff = xwxp + 4 * groups;
-    for (int x = 0; x < 4 * groups; x++) {
-      const uint32_t cx = xt[x] & 0xFFFFu, wx1 = xt[x] >> 16;
-      const uint32_t base = ((shared && (x & 3) < 3) ? xt[x & ~3] : cx) & 0xFFFCu;   // byte offset of the aligned dword pair
-      xoff[x] = base;
-      xsel[x] = 0x0c010c00u + (cx - base) * 0x00010001u;   // pair bytes (cx - base, cx - base + 1) -> u16 lanes, zeros between
-      xwxp[x] = (256u - wx1) | (wx1 << 16);
-    }
-    uint32_t* ytab = xoff + 4 * groups;
-    make_table(g.lv[l - 1].h, L.h, ytab);
-    // ---- tables of the fused form (the walker of level l - 1 makes this level): valid if every source row is the
-    // upper tap of at most one output row, the shared-pair column form holds, and every strip's groups fit its window
-    const OrbLevelInfo& Ls = g.lv[l - 1];
-    bool fused = shared && Ls.wk_rows <= kWkMaxRows && Ls.h < 65536;
-    if ((long long)L.pitch * L.h >= (long long)kRzNoStore) fused = false;   // the offset of a dropped store must lie past the level
-    uint32_t* yemit = htab.data() + L.tab_yemit;
-    uint32_t* xstrip = htab.data() + L.tab_xstrip;
-    for (int y = 0; y < L.h; y++) {
-      const uint32_t sy = ytab[y] & 0xFFFFu, w1 = ytab[y] >> 16;
-      if (sy >= (uint32_t)Ls.h || yemit[sy] != 0u || w1 > 256u) { fused = false; break; }
-      yemit[sy] = 0x80000000u | (w1 << 16) | (uint32_t)y;
-    }
-    // group gq belongs to the last strip whose window starts at or before its first pair
-    for (int c = 0; c <= Ls.wk_nx; c++) xstrip[c] = (uint32_t)groups;
-    for (int gq = groups - 1; gq >= 0; gq--) {
-      const uint32_t b0 = xoff[4 * gq], b3 = xoff[4 * gq + 3];
-      int c = (int)(b0 / (uint32_t)Ls.wk_px);
-      if (c > Ls.wk_nx - 1) c = Ls.wk_nx - 1;
-      const uint32_t xs = (uint32_t)(c * Ls.wk_px);
-      // every tap that counts lies inside the 256-px window; the second dword of a pair may stick out of it (it then
-      // holds only weight-0 taps: the replicated last pixel) -- the read stays inside the wave's LDS block
-      if (b0 < xs || b3 < b0 || b3 + 4u > xs + 256u) fused = false;
-      for (int k = 0; k < 4; k++) {
-        const uint32_t cx = xt[4 * gq + k] & 0xFFFFu, w1 = xt[4 * gq + k] >> 16;
-        if (cx < xs || cx >= xs + 256u || (cx + 1u >= xs + 256u && w1 != 0u)) fused = false;
-      }
-      for (int cc = 0; cc <= c; cc++) xstrip[cc] = (uint32_t)gq;       // groups are monotone in b0: the last write is the first group
-    }
-    for (int c = 0; c < Ls.wk_nx; c++)
-      if (xstrip[c + 1] < xstrip[c] || xstrip[c + 1] - xstrip[c] > 64u) fused = false;
-    if (xstrip[0] != 0u) fused = false;
-    if (Ls.wk_nx > kWkMaxNx) fused = false;
-    for (int c = 0; c <= kWkMaxNx; c++) g.lv[l].wk_xg[c] = (int)xstrip[c < Ls.wk_nx ? c : Ls.wk_nx];
-    g.lv[l].wk_fused = fused ? 1 : 0;
-  }
-  const size_t S = (size_t)max_slots, Wk = (size_t)work_frames_;
-  MSF_HIP_TRY(hipMalloc(&d_pyr_, Wk * g.pyr_bytes));
-  MSF_HIP_TRY(hipMalloc(&d_tab_, htab.size() * sizeof(uint32_t)));
-  MSF_HIP_TRY(hipMemcpy(d_tab_, htab.data(), htab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  MSF_HIP_TRY(hipMalloc(&d_cand_cnt_, Wk * kOrbLevels * sizeof(uint32_t)));
-  MSF_HIP_TRY(hipMalloc(&d_tau_, 2 * Wk * kOrbLevels * sizeof(uint32_t)));
+// options -> plan (orb_plan.h) -> allocate -> upload
+std::string OrbPipeline::init(const OrbOptions& o) {
+  max_slots_ = o.max_slots;
+  half_up_ = o.blur_half_up;
+  blur_sum256_ = o.blur_sum256;
+  profile_ = o.profile;
+  force_tau_ = o.dense_fast ? kFastT : 0;
+  stream_min_frames_ = o.stream_min_frames;
+  read_env();
+
+  OrbPlanRequest rq;
+  rq.width = o.width;
+  rq.height = o.height;
+  rq.max_slots = o.max_slots;
+  rq.work_frames = o.work_frames;
+  rq.level_size_mul_inv = o.level_size_mul_inv;
+  rq.resize_generic = resize_generic_;
+  rq.force_tau = force_tau_;
+  rq.stream_min_frames = stream_min_frames_;
+  OrbPlan plan;
+  const std::string err = plan_orb(rq, &plan);
+  if (!err.empty()) return err;
+  g_ = plan.g;
+  prim_ = plan.prim;
+  harris_ = plan.harris;
+  work_frames_ = plan.work_frames;
+  for (int l = 0; l < kOrbLevels; l++) resize_shared_[l] = plan.resize_shared[l];
+
+  const OrbGeometry& g = g_;
+  const size_t S = (size_t)max_slots_, Wk = (size_t)work_frames_;
+  const size_t total = (size_t)(g.pool_base + (long long)g.pool_entries);   // candidate arrays: primary regions + the pool
+  MSF_HIP_TRY(d_pyr_.reserve(Wk * g.pyr_bytes));
+  MSF_HIP_TRY(d_tab_.reserve(plan.tab.size() * sizeof(uint32_t)));
+  MSF_HIP_TRY(hipMemcpy(d_tab_, plan.tab.data(), plan.tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  MSF_HIP_TRY(d_cand_cnt_.reserve(Wk * kOrbLevels * sizeof(uint32_t)));
+  MSF_HIP_TRY(d_tau_.reserve(2 * Wk * kOrbLevels * sizeof(uint32_t)));
   MSF_HIP_TRY(hipMemset(d_tau_, 0, 2 * Wk * kOrbLevels * sizeof(uint32_t)));
-  MSF_HIP_TRY(hipMalloc(&d_redo_, (1 + Wk * kOrbLevels) * sizeof(uint32_t)));   // the dense-pass queue
-  MSF_HIP_TRY(hipMalloc(&d_redo_hist_, Wk * kOrbLevels * 256 * sizeof(uint32_t)));
+  MSF_HIP_TRY(d_redo_.reserve((1 + Wk * kOrbLevels) * sizeof(uint32_t)));   // the dense-pass queue
+  MSF_HIP_TRY(d_redo_hist_.reserve(Wk * kOrbLevels * 256 * sizeof(uint32_t)));
   MSF_HIP_TRY(hipMemset(d_redo_hist_, 0, Wk * kOrbLevels * 256 * sizeof(uint32_t)));   // k_redo_thr leaves it zeroed
-  MSF_HIP_TRY(hipMalloc(&d_redo_thr_, Wk * kOrbLevels * sizeof(uint32_t)));
-  MSF_HIP_TRY(hipMalloc(&d_qstat_, Wk * kOrbLevels * kQStat * sizeof(uint32_t)));
+  MSF_HIP_TRY(d_redo_thr_.reserve(Wk * kOrbLevels * sizeof(uint32_t)));
+  MSF_HIP_TRY(d_qstat_.reserve(Wk * kOrbLevels * kQStat * sizeof(uint32_t)));
   MSF_HIP_TRY(hipMemset(d_qstat_, 0, Wk * kOrbLevels * kQStat * sizeof(uint32_t)));
-  {
-    // candidate arrays: a primary region per work row + the pool.  The pool only serves dense CALLS, whose frames lay
-    // their full-capacity regions over it: every row with MSF_FLAG_FAST_DENSE, at most stream_min_frames - 1 frames
-    // otherwise.  (The dense second pass of a streaming call lists into the level's primary list: k_fast_redo.)
-    const long long dense_rows = force_tau_ == kFastT ? (long long)Wk : std::min<long long>((long long)Wk, std::max(stream_min_frames_ - 1, 0));
-    const long long pool_entries_ = std::max<long long>(dense_rows * g.cand_total, 16);
-    g.pool_base = (long long)Wk * g.prim_total;
-    const long long total = g.pool_base + pool_entries_;
-    if (total >= (1ll << 32)) return "ORB candidate arrays exceed 2^32 entries: reduce max_batch_pairs";
-    g.pool_entries = (unsigned)pool_entries_;
-    MSF_HIP_TRY(hipMalloc(&d_cand_, (size_t)total * sizeof(uint32_t)));
-    MSF_HIP_TRY(hipMalloc(&d_cand_sc_, (size_t)total));
-    MSF_HIP_TRY(hipMalloc(&d_cmap_, Wk * kOrbLevels * sizeof(uint2)));
-    MSF_HIP_TRY(hipMemset(d_cmap_, 0, Wk * kOrbLevels * sizeof(uint2)));
-  }
-  MSF_HIP_TRY(hipMalloc(&d_walk_abort_, 16));
+  MSF_HIP_TRY(d_cand_.reserve(total * sizeof(uint32_t)));
+  MSF_HIP_TRY(d_cand_sc_.reserve(total));
+  MSF_HIP_TRY(d_cmap_.reserve(Wk * kOrbLevels * sizeof(uint2)));
+  MSF_HIP_TRY(hipMemset(d_cmap_, 0, Wk * kOrbLevels * sizeof(uint2)));
+  MSF_HIP_TRY(d_walk_abort_.reserve(16));
   MSF_HIP_TRY(hipMemset(d_walk_abort_, 0, 16));
   MSF_HIP_TRY(hipHostMalloc(&h_walk_abort_, 16, hipHostMallocDefault));
   h_walk_abort_[0] = h_walk_abort_[1] = 0u;
-  MSF_HIP_TRY(hipMalloc(&d_s1_cnt_, Wk * kOrbLevels * sizeof(uint32_t)));
-  MSF_HIP_TRY(hipMalloc(&d_s1_, Wk * g.s1_total * sizeof(uint4)));
-  MSF_HIP_TRY(hipMalloc(&d_kp_, S * kKpCap * sizeof(msf_keypoint)));
-  MSF_HIP_TRY(hipMalloc(&d_desc_, S * kKpCap * 32));
-  MSF_HIP_TRY(hipMalloc(&d_kp_cnt_, S * sizeof(uint32_t)));
-  MSF_HIP_TRY(hipMalloc(&d_status_, S * sizeof(uint32_t)));
-  MSF_HIP_TRY(hipMalloc(&d_qres_, (size_t)kSplitMaxPairs * kKpCap * sizeof(uint32_t)));
-  MSF_HIP_TRY(hipMalloc(&d_done_, (size_t)kSplitMaxPairs * sizeof(uint32_t)));
+  MSF_HIP_TRY(d_s1_cnt_.reserve(Wk * kOrbLevels * sizeof(uint32_t)));
+  MSF_HIP_TRY(d_s1_.reserve(Wk * g.s1_total * sizeof(uint4)));
+  MSF_HIP_TRY(d_kp_.reserve(S * kKpCap * sizeof(msf_keypoint)));
+  MSF_HIP_TRY(d_desc_.reserve(S * kKpCap * 32));
+  MSF_HIP_TRY(d_kp_cnt_.reserve(S * sizeof(uint32_t)));
+  MSF_HIP_TRY(d_status_.reserve(S * sizeof(uint32_t)));
+  MSF_HIP_TRY(d_qres_.reserve((size_t)kSplitMaxPairs * kKpCap * sizeof(uint32_t)));
+  MSF_HIP_TRY(d_done_.reserve((size_t)kSplitMaxPairs * sizeof(uint32_t)));
   MSF_HIP_TRY(hipMemset(d_done_, 0, (size_t)kSplitMaxPairs * sizeof(uint32_t)));
   MSF_HIP_TRY(hipMemset(d_kp_cnt_, 0, S * sizeof(uint32_t)));
   MSF_HIP_TRY(hipMemset(d_status_, 0, S * sizeof(uint32_t)));
   MSF_HIP_TRY(hipMemset(d_cand_cnt_, 0, Wk * kOrbLevels * sizeof(uint32_t)));
   MSF_HIP_TRY(hipMemset(d_s1_cnt_, 0, Wk * kOrbLevels * sizeof(uint32_t)));
   MSF_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(c_pattern), k_orb_bit_pattern_31, 1024));
-  {
-    std::vector<uint32_t> disc(2 * kDiscTasks, 0u);   // padding tasks: zero weights
-    for (int v = -15; v <= 15; v++) {
-      const int dmax = g.umax[v < 0 ? -v : v];
-      for (int k = 0; k < 8; k++) {
-        uint32_t wu = 0, w1 = 0;
-        for (int b = 0; b < 4; b++) {
-          const int u = -16 + 4 * k + b;
-          if (u >= -dmax && u <= dmax) {
-            wu |= (uint32_t)(uint8_t)(int8_t)u << (8 * b);
-            w1 |= (uint32_t)(uint8_t)(int8_t)v << (8 * b);
-          }
-        }
-        disc[2 * ((v + 15) * 8 + k)] = wu;
-        disc[2 * ((v + 15) * 8 + k) + 1] = w1;
-      }
-    }
-    MSF_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(c_disc), disc.data(), sizeof(uint32_t) * 2 * kDiscTasks));
-  }
+  MSF_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(c_disc), plan.disc.data(), sizeof(uint32_t) * 2 * kDiscTasks));
   if (profile_) {
     for (auto& set : evr_)
       for (auto& e : set.ev) MSF_HIP_TRY(hipEventCreate(&e));
@@ -2819,17 +2578,8 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
   hipLaunchKernelGGL(k_thr_harris, dim3(g.nlevels, n), dim3(dense ? 256 : 64), 0, st, g, src, d_pyr_,
                      d_cand_cnt_, d_cand_, d_cand_sc_, d_cmap_, d_s1_cnt_, d_s1_, d_status_, dense ? 1 : 0);
   if (!dense) {
-    HarrisUnits hw;
-    int nu = 0;
-    for (int l = 0; l < kOrbLevels; l++) {
-      hw.base[l] = nu;
-      hw.n[l] = l < g.nlevels ? (2 * g.lv[l].quota * 5 / 4 + 63) / 64 : 0;
-      if (l < g.nlevels && hw.n[l] < 1) hw.n[l] = 1;
-      nu += hw.n[l];
-    }
-    hw.base[kOrbLevels] = nu;
-    for (int l = g.nlevels; l < kOrbLevels; l++) hw.base[l] = nu;
-    hw.base[g.nlevels] = nu;
+    const HarrisUnits& hw = harris_;
+    const int nu = hw.base[kOrbLevels];
     hipLaunchKernelGGL(k_harris_flat, dim3((nu + 3) / 4, n), dim3(256), 0, st, g, src, d_pyr_, hw, d_s1_cnt_, d_s1_);
   }
   hipLaunchKernelGGL(k_select, dim3(n), dim3(256), 0, st, g, src.slot0, d_s1_cnt_, d_s1_, d_kp_, d_kp_cnt_,
@@ -2984,9 +2734,9 @@ int OrbPipeline::debug_get(int what, int slot, int level, void* host_out, size_t
       if (cut > 0u) {
         const OrbLevelInfo& L = g.lv[level];
         const size_t cap_l = (size_t)L.cand_cap;
-        uint32_t* d_tmp = nullptr;   // [2] queue (count, item) | [8] counts | [8] uint2 map | keys [cap_l] | scores [cap_l]
+        DevBuf<uint32_t> d_tmp;      // [2] queue (count, item) | [8] counts | [8] uint2 map | keys [cap_l] | scores [cap_l]
         const size_t words = 2 + kOrbLevels + 2 * kOrbLevels + cap_l + (cap_l + 3) / 4;
-        if (hipMalloc(&d_tmp, words * 4) != hipSuccess) return fail("hipMalloc failed in debug_get");
+        if (d_tmp.reserve(words * 4) != hipSuccess) return fail("hipMalloc failed in debug_get");
         if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize failed in debug_get");
         uint32_t head[2 + kOrbLevels + 2 * kOrbLevels] = {};
         head[0] = 1u;
@@ -3016,7 +2766,6 @@ int OrbPipeline::debug_get(int what, int slot, int level, void* host_out, size_t
           e2 = hipMemcpy(tk.data(), d_tmp + 2 + 3 * kOrbLevels, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
           if (e2 == hipSuccess) e2 = hipMemcpy(ts.data(), d_tmp + 2 + 3 * kOrbLevels + cap_l, n, hipMemcpyDeviceToHost);
         }
-        hipFree(d_tmp);
         if (e2 != hipSuccess) return fail("dense FAST pass failed in debug_get");
       }
       std::vector<int32_t> o;

@@ -51,6 +51,7 @@ def lib():
         L.orb_oracle_level_scale.restype = C.c_float
         L.orb_oracle_level_scale.argtypes = [C.c_void_p, C.c_int]
         L.orb_oracle_level_quota.argtypes = [C.c_void_p, C.c_int]
+        L.orb_oracle_umax.argtypes = [C.c_void_p, C.c_int]
         L.orb_oracle_level_pixels.restype = C.c_void_p
         L.orb_oracle_level_pixels.argtypes = [C.c_void_p, C.c_int]
         L.orb_oracle_level_blurred.restype = C.c_void_p
@@ -115,6 +116,9 @@ class OrbOracle:
 
     def level_quota(self, l):
         return self.L.orb_oracle_level_quota(self.ctx, l)
+
+    def umax(self):
+        return [self.L.orb_oracle_umax(self.ctx, v) for v in range(16)]
 
     def level_pixels(self, l, blurred=False):
         w, h = self.level_size(l)

@@ -592,6 +592,7 @@ int orb_oracle_level_size(const orb_oracle_ctx* c, int l, int* w, int* h) {
 }
 float orb_oracle_level_scale(const orb_oracle_ctx* c, int l) { return c->scale[l]; }
 int orb_oracle_level_quota(const orb_oracle_ctx* c, int l) { return c->quota[l]; }
+int orb_oracle_umax(const orb_oracle_ctx* c, int v) { return c->umax[v]; }
 const uint8_t* orb_oracle_level_pixels(const orb_oracle_ctx* c, int l) { return c->lvl[l]; }
 const uint8_t* orb_oracle_level_blurred(const orb_oracle_ctx* c, int l) { return c->blr[l]; }
 int orb_oracle_fast_candidates(const orb_oracle_ctx* c, int l, const int32_t** xys) {

@@ -68,6 +68,7 @@ const uint8_t* orb_oracle_descriptors(const orb_oracle_ctx* c); /* [n][32] */
 int orb_oracle_level_size(const orb_oracle_ctx* c, int level, int* w, int* h);
 float orb_oracle_level_scale(const orb_oracle_ctx* c, int level);
 int orb_oracle_level_quota(const orb_oracle_ctx* c, int level);
+int orb_oracle_umax(const orb_oracle_ctx* c, int v);   /* half width of row v of the ICAngles disc, v = 0..15 */
 const uint8_t* orb_oracle_level_pixels(const orb_oracle_ctx* c, int level);   /* unblurred, stride = w */
 const uint8_t* orb_oracle_level_blurred(const orb_oracle_ctx* c, int level);  /* blurred,   stride = w */
 /* FAST candidates after NMS + border reject, row-major; triplets (x, y, score) */

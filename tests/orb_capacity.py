@@ -1,6 +1,6 @@
 """ORB capacity predicate and hard-input generators (test helper: no pytest import, no GPU).
 
-The ORB path keeps fixed-capacity device lists.  A frame whose result does not fit them comes back loud
+The ORB path keeps fixed-capacity device lists (mono_slam_framework_amd/csrc/orb_plan.h sizes them).  A frame whose result does not fit them comes back loud
 (n_out = -1 / MSF_ERR_CAPACITY); any other frame must come back bit-exact, whatever else is in the call.  `capacity()`
 decides from the CPU oracle (oracle/orb.py) which case a frame is, and the generators below build inputs that sit on either
 side of that line.  tests/test_orb_capacity.py pins what every generator is for, tests/test_orb_capacity_gpu.py holds
@@ -10,7 +10,8 @@ import numpy as np
 
 from oracle import orb as oracle_orb
 
-# The capacities, as mono_slam_framework_amd/csrc/orb_pipeline.h documents them (OrbPipeline::init sizes the lists):
+# The capacities, as mono_slam_framework_amd/csrc/orb_plan.h documents them (plan_orb sizes the lists;
+# tests/test_orb_plan_host.py compares these restatements with the compiled plan):
 KP_CAP = 2048          # kKpCap: final key points of a frame
 S1_CAP = 8192          # kS1Cap: key points of a level kept by retainBest(2N) on the FAST score (ties included)
 

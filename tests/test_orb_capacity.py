@@ -15,10 +15,11 @@ SIZES = [(640, 480), (1280, 720)]
 
 
 def test_helper_caps_are_the_pipeline_caps():
-    src = open(os.path.join(ROOT, "mono_slam_framework_amd", "csrc", "orb_pipeline.h")).read()
+    src = open(os.path.join(ROOT, "mono_slam_framework_amd", "csrc", "orb_plan.h")).read()
     assert int(re.search(r"constexpr int kKpCap = (\d+);", src).group(1)) == oc.KP_CAP
     assert int(re.search(r"constexpr int kS1Cap = (\d+);", src).group(1)) == oc.S1_CAP
-    # the list sizes OrbPipeline::init computes, at the sizes the GPU tests use
+    # the list sizes plan_orb computes, at the sizes the GPU tests use (tests/test_orb_plan_host.py holds the helper to
+    # the compiled plan, level by level)
     assert [oc.full_list(w, h) for (w, h) in [(1280, 720), (1067, 600), (357, 201), (100, 60)]] == [115200, 80032, 8976, 4096]
     assert [oc.primary_list(w, h) for (w, h) in [(1280, 720), (1067, 600), (889, 500), (640, 480), (444, 333), (429, 241)]] == \
         [14400, 10016, 8192, 8192, 8192, 12928]
