@@ -390,8 +390,11 @@ typedef enum msf_debug_what {
   MSF_DBG_LOFTR_ACT = 9,     /* float NCHW activation of one frame of the last backbone pass (the first; msf_debug_loftr_backbone: image
                                 act_image) after ResNet stage
                                 `level` + 1: [8][240][320], [16][120][160], [32][60][80], [32][30][40] (level 0..3) */
-  MSF_DBG_LOFTR_TOK = 11     /* float [2][1200][32] tokens of pair 0 before the transformer (backbone + positional
+  MSF_DBG_LOFTR_TOK = 11,    /* float [2][1200][32] tokens of pair 0 before the transformer (backbone + positional
                                 encoding) of the last match call; MSF_FLAG_KEEP_DEBUG handles only */
+  MSF_DBG_ORB_MATCH_FORM = 12 /* ORB, int32 [2]: {the Hamming 2-NN kernel of the handle's last match launch: 0 none yet,
+                                1 k_match_split (32 workgroups per pair; calls of at most 128 pairs), 2 k_match (one
+                                workgroup per pair); the train chunk in effect (1024, or MSF_ORB_TRAIN_CHUNK)} */
 } msf_debug_what;
 /* copies to host; *n_bytes = bytes available (may exceed cap_bytes, then only cap_bytes are written) */
 int msf_debug_get(msf_handle* h, int32_t what, int32_t slot, int32_t level,
@@ -428,6 +431,16 @@ int msf_debug_loftr_transformer(msf_handle* h, int32_t n_pairs, int32_t first_bl
  * frames that overlap.  n = 0 does nothing.  Not timed by msf_stage_times. */
 int msf_debug_loftr_backbone(msf_handle* h, int32_t n, const uint8_t* d_a, const uint8_t* d_b, int64_t frame_stride,
                              int64_t row_stride, int32_t act_image, float* d_tok_a, float* d_tok_b, void* stream);
+
+/* ORB: the matcher alone (Hamming 2-NN, ratio test, ordered list) on features the caller supplies.  kp [n] and
+ * desc [n][32] are HOST pointers; they are written into feature slot `slot` of the handle (the slots of
+ * msf_extract_device / msf_match_slots_device), the slot's key point count is set to n and its status word cleared (a
+ * slot an extraction left over capacity matches again).  Returns when the copies are complete on the handle's stream;
+ * msf_debug_get(MSF_DBG_KEYPOINTS / MSF_DBG_DESCRIPTORS, slot) returns the bytes that were set, and a match call reads
+ * them exactly as it reads extracted features (only x, y and the descriptor matter to it); MSF_DBG_ORB_MATCH_FORM tells
+ * which of the two match kernels that call launched.  MSF_ERR_INVALID_ARG for a LoFTR handle, slot outside
+ * [0, 2*max_batch_pairs), n outside [0, 2048], a null pointer with n > 0.  Not timed by msf_stage_times. */
+int msf_debug_orb_set_features(msf_handle* h, int32_t slot, int32_t n, const msf_keypoint* kp, const uint8_t* desc);
 
 /* per-stage device time, measured with HIP events on the launch stream (needs MSF_FLAG_PROFILE): the SUM over the batch
  * calls since the previous query -- queried after every call it is that call's times; a caller that enqueues many calls

@@ -1585,6 +1585,22 @@ int msf_debug_loftr_backbone(msf_handle* h, int32_t n, const uint8_t* d_a, const
   });
 }
 
+int msf_debug_orb_set_features(msf_handle* h, int32_t slot, int32_t n, const msf_keypoint* kp, const uint8_t* desc) {
+  return guarded(h, "msf_debug_orb_set_features", [&]() -> int {
+    if (h->cfg.kind != MSF_KIND_ORB) return fail(h, MSF_ERR_INVALID_ARG, "msf_debug_orb_set_features: not an ORB handle");
+    if (slot < 0 || slot >= 2 * h->cfg.max_batch_pairs)
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_debug_orb_set_features: slot outside [0, 2*max_batch_pairs)");
+    if (n < 0 || n > msf::kKpCap) return fail(h, MSF_ERR_INVALID_ARG, "msf_debug_orb_set_features: n outside [0, 2048]");
+    if (n > 0 && (!kp || !desc)) return fail(h, MSF_ERR_INVALID_ARG, "msf_debug_orb_set_features: null pointer with n > 0");
+    CallScope cs{h};
+    if (int rc = cs.enter()) return rc;
+    Drain drain{cs.st};   // the copies read the caller's arrays: never return with one in flight
+    HIP_TRY(h, "orb set_features", h->orb.set_features(slot, n, kp, desc, cs.st));
+    drain.armed = false;
+    return cs.finish();
+  });
+}
+
 int msf_stage_times(msf_handle* h, const char** names, float* ms, int32_t cap) {
   if (!names || !ms || cap < 1) return 0;
   const int n = guarded(h, "msf_stage_times", [&]() -> int {

@@ -2597,6 +2597,31 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
   return hipGetLastError();
 }
 
+// the train chunk in effect: kTrainChunk, or MSF_ORB_TRAIN_CHUNK in [16, kTrainChunk] (read once per process)
+static int train_chunk() {
+  static const int chunk = [] {
+    const char* e = getenv("MSF_ORB_TRAIN_CHUNK");
+    const int v = e ? atoi(e) : kTrainChunk;
+    return v >= 16 && v <= kTrainChunk ? v : kTrainChunk;
+  }();
+  return chunk;
+}
+
+hipError_t OrbPipeline::set_features(int slot, int n, const msf_keypoint* kp, const uint8_t* desc, hipStream_t st) {
+  hipError_t e = hipSuccess;
+  if (n > 0) {
+    e = hipMemcpyAsync(d_kp_ + (size_t)slot * kKpCap, kp, (size_t)n * sizeof(msf_keypoint), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return e;
+    e = hipMemcpyAsync(d_desc_ + (size_t)slot * kKpCap * 32, desc, (size_t)n * 32, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return e;
+  }
+  set_words_[0] = (uint32_t)n;
+  set_words_[1] = 0u;
+  e = hipMemcpyAsync(d_kp_cnt_ + slot, &set_words_[0], sizeof(uint32_t), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return e;
+  return hipMemcpyAsync(d_status_ + slot, &set_words_[1], sizeof(uint32_t), hipMemcpyHostToDevice, st);
+}
+
 hipError_t OrbPipeline::match(int n_pairs, const int32_t* d_slot_a, const int32_t* d_slot_b, float ratio,
                               msf_match* d_out, int cap, int32_t* d_n_out, hipStream_t st, int slot_base, int slot_limit) {
   if (n_pairs <= 0) return hipSuccess;
@@ -2607,12 +2632,10 @@ hipError_t OrbPipeline::match(int n_pairs, const int32_t* d_slot_a, const int32_
     ev_begin_call();                      // a slot-pair match on its own is a call of its own
     hipEventRecord(ev_[4], st);
   }
-  static const int chunk = [] {
-    const char* e = getenv("MSF_ORB_TRAIN_CHUNK");
-    const int v = e ? atoi(e) : kTrainChunk;
-    return v >= 16 && v <= kTrainChunk ? v : kTrainChunk;
-  }();
-  if (n_pairs <= kSplitMaxPairs && d_qres_)
+  const int chunk = train_chunk();
+  const bool split = n_pairs <= kSplitMaxPairs && d_qres_;
+  last_match_form_ = split ? 1 : 2;
+  if (split)
     hipLaunchKernelGGL(k_match_split, dim3(kSplitBlocks, n_pairs), dim3(256), 0, st, n_pairs, d_slot_a, d_slot_b, d_kp_,
                        d_kp_cnt_, d_desc_, d_status_, ratio, d_out, cap, d_n_out, chunk, d_qres_, d_done_, slot_base, limit);
   else
@@ -2684,6 +2707,12 @@ int OrbPipeline::debug_get(int what, int slot, int level, void* host_out, size_t
   if (what == MSF_DBG_LEVEL_SIZES) {
     int32_t v[kOrbLevels][4];
     for (int l = 0; l < kOrbLevels; l++) { v[l][0] = g.lv[l].w; v[l][1] = g.lv[l].h; v[l][2] = g.lv[l].pitch; v[l][3] = g.lv[l].quota; }
+    *n_bytes = sizeof(v);
+    memcpy(host_out, v, sizeof(v) < cap ? sizeof(v) : cap);
+    return 0;
+  }
+  if (what == MSF_DBG_ORB_MATCH_FORM) {
+    const int32_t v[2] = {last_match_form_, train_chunk()};
     *n_bytes = sizeof(v);
     memcpy(host_out, v, sizeof(v) < cap ? sizeof(v) : cap);
     return 0;

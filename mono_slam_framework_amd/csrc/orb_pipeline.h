@@ -57,6 +57,9 @@ class OrbPipeline {
   hipError_t match(int n_pairs, const int32_t* d_slot_a, const int32_t* d_slot_b, float ratio,
                    msf_match* d_out, int cap_per_pair, int32_t* d_n_out, hipStream_t st, int slot_base = 0,
                    int slot_limit = 0);
+  // debug (msf_debug_orb_set_features): n <= kKpCap caller features (HOST pointers) into feature slot `slot`, its count
+  // set to n and its status word cleared; enqueued on `st`, the caller waits before kp / desc go away
+  hipError_t set_features(int slot, int n, const msf_keypoint* kp, const uint8_t* desc, hipStream_t st);
 
   const OrbGeometry& geom() const { return g_; }
   int max_slots() const { return max_slots_; }
@@ -112,6 +115,8 @@ class OrbPipeline {
   DevBuf<uint32_t> d_status_;   // [slots]
   DevBuf<uint32_t> d_qres_;     // [kSplitMaxPairs][kKpCap] per-query results of the small-batch matcher
   DevBuf<uint32_t> d_done_;     // [kSplitMaxPairs] ticket counters (left at 0)
+  int last_match_form_ = 0;     // the last match launch: 0 none yet, 1 k_match_split, 2 k_match (MSF_DBG_ORB_MATCH_FORM)
+  uint32_t set_words_[2] = {};  // set_features: the count and the status word while their copies are in flight
   // Stage events (MSF_FLAG_PROFILE).  A RING of event sets: a call records into the next free set and nobody waits, so a
   // caller can enqueue many batches ahead of the device; stage_times() harvests every finished set and returns the SUM
   // of the stage times since the last query (a query after every call sees that call's times, as before).  A set that

@@ -634,6 +634,28 @@ class FeatureMatcher(_Matcher):
     def descriptors(self, slot, cache=False):
         return self._debug(_lib.DBG_DESCRIPTORS, self._slot(slot, cache), 0, np.uint8, 2048 * 32).reshape(-1, 32)
 
+    def set_features(self, slot, kp, desc):
+        """Debug (msf_debug_orb_set_features): writes caller features into feature slot `slot` of [0, 2 * max_batch_pairs)
+        -- the slots match_slots_device pairs and keypoints(slot, cache=True) reads.  kp: KP_DTYPE [n], or float [n, 2]
+        (x, y; the other fields zero); desc: uint8 [n, 32]; n <= 2048."""
+        kp = np.asarray(kp)
+        if kp.dtype != _lib.KP_DTYPE:
+            xy = np.asarray(kp, np.float32).reshape(-1, 2)
+            kp = np.zeros(len(xy), _lib.KP_DTYPE)
+            kp["x"], kp["y"] = xy[:, 0], xy[:, 1]
+        kp = np.ascontiguousarray(kp.reshape(-1))
+        desc = np.ascontiguousarray(np.asarray(desc, np.uint8).reshape(-1, 32))
+        if len(desc) != len(kp):
+            raise ValueError("one descriptor per key point")
+        self._check(self._L.msf_debug_orb_set_features(self._h, slot, len(kp), kp.ctypes.data if len(kp) else None,
+                                                       desc.ctypes.data if len(kp) else None))
+
+    def match_form(self):
+        """(form, chunk): the kernel of this handle's last match launch -- 0 none yet, 1 k_match_split (calls of at most
+        128 pairs), 2 k_match -- and the train chunk in effect (1024, or MSF_ORB_TRAIN_CHUNK)."""
+        v = self._debug(_lib.DBG_ORB_MATCH_FORM, 0, 0, np.int32, 8)
+        return int(v[0]), int(v[1])
+
 
 class DNNFeatureMatcher(_Matcher):
     """LoFTR_teacher (model/LoFTR_teacher.onnx restated as HIP kernels) + threshold + decode, on the GPU.

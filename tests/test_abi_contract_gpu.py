@@ -97,6 +97,7 @@ def test_null_handle(orb):
         "msf_debug_loftr_head": lambda: L.msf_debug_loftr_head(z, 1, z, z, z, 16, z, z),
         "msf_debug_loftr_transformer": lambda: L.msf_debug_loftr_transformer(z, 1, 0, 8, z, z, z, z, z),
         "msf_debug_loftr_backbone": lambda: L.msf_debug_loftr_backbone(z, 1, z, z, 0, 0, 0, z, z, z),
+        "msf_debug_orb_set_features": lambda: L.msf_debug_orb_set_features(z, 0, 0, z, z),
         "msf_set_mappoints": lambda: L.msf_set_mappoints(z, 0, z, 0),
         "msf_count_mappoint_matches_device": lambda: L.msf_count_mappoint_matches_device(z, 1, z, 16, z, z, z, z, z),
         "msf_store_frame": lambda: L.msf_store_frame(z, 0, None),
@@ -169,6 +170,18 @@ def test_bad_arguments_and_the_call_after(orb, loftr, frames):
     la, lb = synth.synth_pair(60, 640, 480, mode=1, shift=(32, 16))
     ld = _device_frames(np.stack([la, la]), np.stack([lb, lb]), 640)
     batch0 = _lib.RansacBatch(struct_size=0)
+    fk = np.zeros(4, _lib.KP_DTYPE)
+    fk["x"], fk["y"], fk["octave"] = [1.5, 2.5, 3.5, 4.5], [9, 8, 7, 6], [0, 1, 2, 3]
+    fd = np.arange(4 * 32, dtype=np.uint8).reshape(4, 32)
+    pk, pd = fk.ctypes.data, fd.ctypes.data
+    set_features = "msf_debug_orb_set_features"
+
+    def good_set_features():
+        orb.set_features(2 * P - 1, fk, fd)                  # the last caller slot
+        assert orb.keypoints(2 * P - 1, cache=True).tobytes() == fk.tobytes()
+        np.testing.assert_array_equal(orb.descriptors(2 * P - 1, cache=True), fd)
+        orb.set_features(0, fk[:0], fd[:0])                  # n = 0 with null pointers
+        assert len(orb.keypoints(0, cache=True)) == 0
 
     def good_find_models_device(mt):
         r = mt.find_models_device(d_out, d_n, n_hyp=8, seed=1)
@@ -203,6 +216,7 @@ def test_bad_arguments_and_the_call_after(orb, loftr, frames):
         "msf_debug_loftr_head": lambda: loftr.head_device(feat[0], feat[1], lo, ln),
         "msf_debug_loftr_transformer": lambda: loftr.transformer_device(feat[0], feat[1], feat_o[0], feat_o[1], 0, 2),
         "msf_debug_loftr_backbone": lambda: loftr.backbone_device(ld[0], ld[1], tok[0], tok[1], act_image=3),
+        set_features: good_set_features,
     }
     bad_arg = lambda e: e + ": bad argument"                                                     # noqa: E731
     # (handle, entry whose good call follows, what is wrong, call, status, text left in msf_last_error)
@@ -282,6 +296,20 @@ def test_bad_arguments_and_the_call_after(orb, loftr, frames):
         (orb, "msf_debug_loftr_backbone", "ORB handle",
          lambda: L.msf_debug_loftr_backbone(h, 1, dA, dB, fs, PITCH, 0, tok[0].data_ptr(), tok[1].data_ptr(), None),
          INV, "msf_debug_loftr_backbone: not a LoFTR handle"),
+        (loftr, set_features, "LoFTR handle", lambda: L.msf_debug_orb_set_features(lh, 0, 4, pk, pd),
+         INV, set_features + ": not an ORB handle"),
+        (orb, set_features, "slot = 2 * max_batch_pairs", lambda: L.msf_debug_orb_set_features(h, 2 * P, 4, pk, pd),
+         INV, set_features + ": slot outside [0, 2*max_batch_pairs)"),
+        (orb, set_features, "slot = -1", lambda: L.msf_debug_orb_set_features(h, -1, 4, pk, pd),
+         INV, set_features + ": slot outside [0, 2*max_batch_pairs)"),
+        (orb, set_features, "n = 2049", lambda: L.msf_debug_orb_set_features(h, 0, 2049, pk, pd),
+         INV, set_features + ": n outside [0, 2048]"),
+        (orb, set_features, "n = -1", lambda: L.msf_debug_orb_set_features(h, 0, -1, pk, pd),
+         INV, set_features + ": n outside [0, 2048]"),
+        (orb, set_features, "null key points with n > 0", lambda: L.msf_debug_orb_set_features(h, 0, 4, None, pd),
+         INV, set_features + ": null pointer with n > 0"),
+        (orb, set_features, "null descriptors with n > 0", lambda: L.msf_debug_orb_set_features(h, 0, 4, pk, None),
+         INV, set_features + ": null pointer with n > 0"),
         (loftr, "loftr msf_match_batch_device", "n_pairs > max_batch_pairs",
          lambda: L.msf_match_batch_device(lh, P + 1, ld[0].data_ptr(), ld[1].data_ptr(), 640 * 480, 640, lo.data_ptr(), 64,
                                           ln.data_ptr(), None), INV, "n_pairs exceeds max_batch_pairs"),
@@ -316,7 +344,8 @@ def test_bad_arguments_and_the_call_after(orb, loftr, frames):
         before = _err(mt)
         assert call() == status, label
         assert _err(mt) == (before if text is None else text), label
-        if mt is loftr or not entry.startswith("msf_debug_loftr"):      # (an ORB handle has no good call of those)
+        # (an ORB handle has no good call of the LoFTR stage entries, a LoFTR handle none of the ORB one)
+        if not entry.startswith("msf_debug_orb" if mt is loftr else "msf_debug_loftr"):
             good[entry]()
     # every entry with an argument check of its own has a refusal above whose text starts with the entry's name
     named = {e.split()[-1] for _, e, _, _, _, t in cases if t and t.startswith(e.split()[-1] + ":")}

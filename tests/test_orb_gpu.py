@@ -357,8 +357,9 @@ def test_adversarial_density_is_exact_or_loud(name, img):
 
 
 def test_chunked_match_path():
-    """k_match stages train descriptors through LDS in chunks (1024 by default, reached only with heavy ties);
-    a child process shrinks the chunk so ~500 keypoints cross several chunks, and must still be bit-exact."""
+    """k_match_split -- the kernel of a one-pair call; tests/test_orb_match_gpu.py runs k_match -- stages train descriptors
+    through LDS in chunks (1024 by default, reached only with heavy ties); a child process shrinks the chunk so ~500
+    keypoints cross several chunks, and must still be bit-exact."""
     import subprocess
     import sys
     code = (
@@ -368,7 +369,9 @@ def test_chunked_match_path():
         "from mono_slam_framework_amd.matcher import FeatureMatcher\n"
         "from oracle import orb\n"
         "a, b = synth.synth_pair(21, 640, 480)\n"
-        "got = FeatureMatcher(0.8, 640, 480).MatchFrames(a, b)\n"
+        "fm = FeatureMatcher(0.8, 640, 480)\n"
+        "got = fm.MatchFrames(a, b)\n"
+        "assert fm.match_form() == (1, 96), fm.match_form()\n"
         "exp = orb.FeatureMatcherOracle(0.8).MatchFrames(a, b)\n"
         "assert len(exp) > 100 and np.array_equal(got, exp)\n"
     ) % ROOT
