@@ -13,19 +13,12 @@
 #pragma once
 
 #include <cstdint>
-#include <cstring>
 #include <vector>
 
+#include "hip_mirror_types.h"
 #include "msf_local_mapping.h"
 
 namespace msf {
-
-#ifndef MSF_POINT3F_DEFINED
-#define MSF_POINT3F_DEFINED
-struct Point3f {   // cv::Point3f
-  float x, y, z;
-};
-#endif
 
 struct Neighbour {   // vpNeighKFs[i]: where msf_store_frame put its image, and its pose
   int32_t slot;
@@ -60,14 +53,10 @@ inline bool NewMapPoints(msf_handle* handle, int32_t current_slot, const msf_vie
   }
   std::vector<msf_match> matches(n * static_cast<size_t>(cap));
   std::vector<msf_new_point> packed(n * static_cast<size_t>(cap));
-  msf_new_points_params prm;
-  std::memset(&prm, 0, sizeof prm);
-  prm.struct_size = sizeof prm;
+  msf_new_points_params prm = sized<msf_new_points_params>();
   prm.max_cos_parallax = minParallax;
   prm.chi2 = 5.991;
-  msf_new_points_result out;
-  std::memset(&out, 0, sizeof out);
-  out.struct_size = sizeof out;
+  msf_new_points_result out = sized<msf_new_points_result>();
   out.n_new = n_new.data();
   out.packed = packed.data();
   const int rc = msf_create_map_points(handle, current_slot, &current_view, static_cast<int32_t>(n), slots.data(),

@@ -15,33 +15,16 @@
 // float[16].  See INTEGRATION.md.
 #pragma once
 
-#ifndef __HIP_PLATFORM_AMD__
-#define __HIP_PLATFORM_AMD__ 1
-#endif
-#include <hip/hip_runtime_api.h>
-
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
+#include "hip_device_block.h"
+#include "hip_mirror_types.h"
 #include "msf_pose.h"
 
 namespace msf {
-
-#ifndef MSF_POINT3F_DEFINED
-#define MSF_POINT3F_DEFINED
-struct Point3f {   // cv::Point3f
-  float x, y, z;
-};
-#endif
-
-#ifndef MSF_POINT2F_DEFINED
-#define MSF_POINT2F_DEFINED
-struct Point2f {   // cv::Point2f
-  float x, y;
-};
-#endif
 
 class Optimizer {
  public:
@@ -56,9 +39,7 @@ class Optimizer {
     int32_t n_good = 0, rounds = 0;
     float optimised[12];
     std::vector<uint8_t> flags(n > 0 ? n : 1, 0);
-    msf_pose_result out;
-    std::memset(&out, 0, sizeof out);
-    out.struct_size = sizeof out;
+    msf_pose_result out = sized<msf_pose_result>();
     out.n_good = &n_good, out.rounds_run = &rounds, out.Tcw = optimised, out.outliers = flags.data();
     const int rc = msf_pose_optimize(handle, n, n ? &points[0].x : nullptr, n ? &pixels[0].x : nullptr, Tcw, nullptr, &prm, &out);
     if (rc != MSF_OK) return -1;
@@ -83,58 +64,55 @@ class Optimizer {
     if (!L) return true;
     size_t cap = 1;
     for (const Candidate& c : candidates) cap = std::max(cap, std::min(c.points->size(), c.pixels->size()));
-    std::vector<float> p3(L * cap * 3, 0.0f), p2(L * cap * 2, 0.0f), t0(L * 12);
-    std::vector<int32_t> n(L);
+    // one block: the lists, their lengths and entry poses, then n_good, rounds_run, Tcw and the flags
+    struct View {
+      float *p3d, *p2d, *Tcw0;
+      int32_t* n;
+      size_t inputs_end;
+      msf_pose_result out;
+    };
+    DeviceBlock mem;
+    View dev, host;
+    const auto layout = [&](Carver& c) {
+      View v;
+      v.p3d = c.take<float>(L * cap * 3);
+      v.p2d = c.take<float>(L * cap * 2);
+      v.n = c.take<int32_t>(L);
+      v.Tcw0 = c.take<float>(L * 12);
+      v.inputs_end = c.off;
+      v.out = sized<msf_pose_result>();
+      v.out.n_good = c.take<int32_t>(L);
+      v.out.rounds_run = c.take<int32_t>(L);
+      v.out.Tcw = c.take<float>(L * 12);
+      v.out.outliers = c.take<uint8_t>(L * cap);
+      return v;
+    };
+    if (!mem.place(layout, &dev, &host)) return false;
     for (size_t l = 0; l < L; l++) {
       const Candidate& c = candidates[l];
-      n[l] = static_cast<int32_t>(std::min(c.points->size(), c.pixels->size()));
-      if (n[l]) std::memcpy(&p3[l * cap * 3], c.points->data(), n[l] * sizeof(Point3f));
-      if (n[l]) std::memcpy(&p2[l * cap * 2], c.pixels->data(), n[l] * sizeof(Point2f));
-      std::memcpy(&t0[l * 12], c.Tcw, 48);
+      const size_t n = std::min(c.points->size(), c.pixels->size());
+      host.n[l] = static_cast<int32_t>(n);
+      if (n) std::memcpy(host.p3d + l * cap * 3, c.points->data(), n * sizeof(Point3f));
+      if (n) std::memcpy(host.p2d + l * cap * 2, c.pixels->data(), n * sizeof(Point2f));
+      std::memcpy(host.Tcw0 + l * 12, c.Tcw, 48);
     }
-    // one block: the inputs, then n_good, rounds_run, Tcw and the flags
-    const size_t sizes[] = {p3.size() * 4, p2.size() * 4, n.size() * 4, t0.size() * 4, L * 4, L * 4, L * 48, L * cap};
-    size_t off[9] = {0};
-    for (int k = 0; k < 8; k++) off[k + 1] = off[k] + ((sizes[k] + 255) & ~static_cast<size_t>(255));
-    char* base = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&base), off[8]) != hipSuccess) return false;
-    bool ok = hipMemcpy(base + off[0], p3.data(), sizes[0], hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(base + off[1], p2.data(), sizes[1], hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(base + off[2], n.data(), sizes[2], hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(base + off[3], t0.data(), sizes[3], hipMemcpyHostToDevice) == hipSuccess;
     const msf_pose_params prm = Params(intrinsics, chi2);
-    msf_pose_result out;
-    std::memset(&out, 0, sizeof out);
-    out.struct_size = sizeof out;
-    out.n_good = reinterpret_cast<int32_t*>(base + off[4]);
-    out.rounds_run = reinterpret_cast<int32_t*>(base + off[5]);
-    out.Tcw = reinterpret_cast<float*>(base + off[6]);
-    out.outliers = reinterpret_cast<uint8_t*>(base + off[7]);
-    ok = ok && msf_pose_optimize_device(handle, static_cast<int32_t>(L), reinterpret_cast<const float*>(base + off[0]),
-                                        reinterpret_cast<const float*>(base + off[1]), static_cast<int32_t>(cap),
-                                        reinterpret_cast<const int32_t*>(base + off[2]),
-                                        reinterpret_cast<const float*>(base + off[3]), 12, nullptr, 0, &prm, &out,
-                                        nullptr) == MSF_OK;
-    std::vector<int32_t> n_good(L), rounds(L);
-    std::vector<float> tcw(L * 12);
-    std::vector<uint8_t> flags(L * cap);
-    void* host[] = {n_good.data(), rounds.data(), tcw.data(), flags.data()};
-    for (int k = 0; k < 4 && ok; k++) ok = hipMemcpy(host[k], base + off[4 + k], sizes[4 + k], hipMemcpyDeviceToHost) == hipSuccess;
-    hipFree(base);
-    if (!ok) return false;
+    if (!mem.upload() ||
+        msf_pose_optimize_device(handle, static_cast<int32_t>(L), dev.p3d, dev.p2d, static_cast<int32_t>(cap), dev.n,
+                                 dev.Tcw0, 12, nullptr, 0, &prm, &dev.out, nullptr) != MSF_OK ||
+        !mem.download())
+      return false;
     for (size_t l = 0; l < L; l++) {
       Candidate& c = candidates[l];
-      Report(n[l], &flags[l * cap], rounds[l], &tcw[l * 12], c.Tcw, *c.outliers);
-      c.n_good = n_good[l];
+      Report(host.n[l], host.out.outliers + l * cap, host.out.rounds_run[l], host.out.Tcw + l * 12, c.Tcw, *c.outliers);
+      c.n_good = host.out.n_good[l];
     }
     return true;
   }
 
  private:
   static msf_pose_params Params(const float intrinsics[4], float chi2) {
-    msf_pose_params prm;
-    std::memset(&prm, 0, sizeof prm);
-    prm.struct_size = sizeof prm;
+    msf_pose_params prm = sized<msf_pose_params>();
     prm.fx = intrinsics[0], prm.fy = intrinsics[1], prm.cx = intrinsics[2], prm.cy = intrinsics[3];
     prm.chi2 = chi2;
     return prm;

@@ -19,35 +19,18 @@
 // mvP3Dw, mvP2D, mvKeyPointIndices and the number of matches.  See INTEGRATION.md.
 #pragma once
 
-#ifndef __HIP_PLATFORM_AMD__
-#define __HIP_PLATFORM_AMD__ 1
-#endif
-#include <hip/hip_runtime_api.h>
-
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
+#include "hip_device_block.h"
+#include "hip_mirror_types.h"
 #include "msf_pnp.h"
 #include "pnp_solve.h"   // draw_set4: the minimum sets are drawn here and handed to the call
 
 namespace msf {
-
-#ifndef MSF_POINT3F_DEFINED
-#define MSF_POINT3F_DEFINED
-struct Point3f {   // cv::Point3f
-  float x, y, z;
-};
-#endif
-
-#ifndef MSF_POINT2F_DEFINED
-#define MSF_POINT2F_DEFINED
-struct Point2f {   // cv::Point2f
-  float x, y;
-};
-#endif
 
 class PnPsolver {
  public:
@@ -143,70 +126,61 @@ class PnPsolver {
       cap = std::max(cap, s->p3d_.size());
     }
     const int max_records = kMaxRecords;
-    std::vector<float> p3(L * cap * 3, 0.0f), p2(L * cap * 2, 0.0f);
-    std::vector<int32_t> n(L), sets(L * its * 4, 0);
+    const size_t recs = L * max_records;
+    // one block: the lists, their lengths and minimum sets, then the outputs the cache keeps
+    struct View {
+      float *p3d, *p2d;
+      int32_t *n, *sets;
+      size_t inputs_end;
+      msf_pnp_result out;
+    };
+    DeviceBlock mem;
+    View dev, host;
+    const auto layout = [&](Carver& c) {
+      View v;
+      v.p3d = c.take<float>(L * cap * 3);
+      v.p2d = c.take<float>(L * cap * 2);
+      v.n = c.take<int32_t>(L);
+      v.sets = c.take<int32_t>(L * its * 4);
+      v.inputs_end = c.off;
+      v.out = sized<msf_pnp_result>();
+      v.out.n_records = c.take<int32_t>(L);
+      v.out.counts = c.take<int32_t>(L * its);
+      v.out.iteration = c.take<int32_t>(recs);
+      v.out.n_inliers = c.take<int32_t>(recs);
+      v.out.n_refined = c.take<int32_t>(recs);
+      v.out.Tcw_best = c.take<float>(recs * 12);
+      v.out.Tcw_refined = c.take<float>(recs * 12);
+      v.out.inliers_best = c.take<uint8_t>(recs * cap);
+      v.out.inliers_refined = c.take<uint8_t>(recs * cap);
+      return v;
+    };
+    if (!mem.place(layout, &dev, &host)) return false;
     for (size_t l = 0; l < L; l++) {
       const PnPsolver* s = solvers[l];
-      n[l] = static_cast<int32_t>(s->p3d_.size());
-      if (n[l]) std::memcpy(&p3[l * cap * 3], s->p3d_.data(), n[l] * sizeof(Point3f));
-      if (n[l]) std::memcpy(&p2[l * cap * 2], s->p2d_.data(), n[l] * sizeof(Point2f));
-      if (n[l] >= 4)
-        for (int it = 0; it < its; it++) pnp::draw_set4(s->seed_, s->key_, it, n[l], &sets[(l * its + it) * 4]);
+      const int32_t n = host.n[l] = static_cast<int32_t>(s->p3d_.size());
+      if (n) std::memcpy(host.p3d + l * cap * 3, s->p3d_.data(), n * sizeof(Point3f));
+      if (n) std::memcpy(host.p2d + l * cap * 2, s->p2d_.data(), n * sizeof(Point2f));
+      if (n >= 4)
+        for (int it = 0; it < its; it++) pnp::draw_set4(s->seed_, s->key_, it, n, host.sets + (l * its + it) * 4);
     }
-    // one block: inputs, then the outputs the cache keeps
-    const size_t recs = L * max_records;
-    const size_t sizes[] = {p3.size() * 4, p2.size() * 4, n.size() * 4, sets.size() * 4, L * 4, L * its * 4,
-                            recs * 4, recs * 4, recs * 4, recs * 48, recs * 48, recs * cap, recs * cap};
-    size_t off[14] = {0};
-    for (int k = 0; k < 13; k++) off[k + 1] = off[k] + ((sizes[k] + 255) & ~static_cast<size_t>(255));
-    char* base = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&base), off[13]) != hipSuccess) return false;
-    bool ok = hipMemcpy(base + off[0], p3.data(), sizes[0], hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(base + off[1], p2.data(), sizes[1], hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(base + off[2], n.data(), sizes[2], hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(base + off[3], sets.data(), sizes[3], hipMemcpyHostToDevice) == hipSuccess;
     msf_pnp_params prm = solvers[0]->Params(its, max_records);
     prm.min_inliers = floor;
-    msf_pnp_result out;
-    std::memset(&out, 0, sizeof out);
-    out.struct_size = sizeof out;
-    out.n_records = reinterpret_cast<int32_t*>(base + off[4]);
-    out.counts = reinterpret_cast<int32_t*>(base + off[5]);
-    out.iteration = reinterpret_cast<int32_t*>(base + off[6]);
-    out.n_inliers = reinterpret_cast<int32_t*>(base + off[7]);
-    out.n_refined = reinterpret_cast<int32_t*>(base + off[8]);
-    out.Tcw_best = reinterpret_cast<float*>(base + off[9]);
-    out.Tcw_refined = reinterpret_cast<float*>(base + off[10]);
-    out.inliers_best = reinterpret_cast<uint8_t*>(base + off[11]);
-    out.inliers_refined = reinterpret_cast<uint8_t*>(base + off[12]);
-    ok = ok && msf_pnp_ransac_device(h, static_cast<int32_t>(L), reinterpret_cast<const float*>(base + off[0]),
-                                     reinterpret_cast<const float*>(base + off[1]), static_cast<int32_t>(cap),
-                                     reinterpret_cast<const int32_t*>(base + off[2]), &prm,
-                                     reinterpret_cast<const int32_t*>(base + off[3]), &out, nullptr) == MSF_OK;
-    std::vector<int32_t> n_records(L), counts(L * its), iteration(recs), n_inliers(recs), n_refined(recs);
-    std::vector<float> tb(recs * 12), tr(recs * 12);
-    std::vector<uint8_t> ib(recs * cap), ir(recs * cap);
-    void* host[] = {n_records.data(), counts.data(), iteration.data(), n_inliers.data(), n_refined.data(),
-                    tb.data(),        tr.data(),     ib.data(),        ir.data()};
-    for (int k = 0; k < 9 && ok; k++)
-      ok = hipMemcpy(host[k], base + off[4 + k], sizes[4 + k], hipMemcpyDeviceToHost) == hipSuccess;
-    hipFree(base);
-    if (!ok) return false;
+    if (!mem.upload() ||
+        msf_pnp_ransac_device(h, static_cast<int32_t>(L), dev.p3d, dev.p2d, static_cast<int32_t>(cap), dev.n, &prm,
+                              dev.sets, &dev.out, nullptr) != MSF_OK ||
+        !mem.download())
+      return false;
+    const msf_pnp_result& got = host.out;
     for (size_t l = 0; l < L; l++) {
       PnPsolver* s = solvers[l];
-      if (n_records[l] < 0 || n_records[l] > max_records) continue;   // no list, or too many records: the solver asks itself
-      s->counts_.assign(counts.begin() + l * its, counts.begin() + (l + 1) * its);
-      s->sets_.assign(sets.begin() + l * its * 4, sets.begin() + (l + 1) * its * 4);
+      if (got.n_records[l] < 0 || got.n_records[l] > max_records) continue;   // no list, or too many records: the solver asks itself
+      s->counts_.assign(got.counts + l * its, got.counts + (l + 1) * its);
+      s->sets_.assign(host.sets + l * its * 4, host.sets + (l + 1) * its * 4);
       s->records_.clear();
-      for (int r = 0; r < n_records[l]; r++) {
+      for (int r = 0; r < got.n_records[l]; r++) {
         const size_t at = l * max_records + r;
-        if (n_inliers[at] < s->floor_) continue;   // a record of the call's lower floor only
-        s->records_.push_back(Record{iteration[at], n_inliers[at], n_refined[at], {}, {}, {}, {}});
-        Record& rec = s->records_.back();
-        std::memcpy(rec.Tcw_best, &tb[at * 12], 48);
-        std::memcpy(rec.Tcw_refined, &tr[at * 12], 48);
-        rec.inliers_best.assign(ib.begin() + at * cap, ib.begin() + at * cap + n[l]);
-        rec.inliers_refined.assign(ir.begin() + at * cap, ir.begin() + at * cap + n[l]);
+        if (got.n_inliers[at] >= s->floor_) s->records_.push_back(s->RecordAt(got, at, cap));   // else: of the call's lower floor only
       }
       s->cached_ = its;
     }
@@ -230,9 +204,7 @@ class PnPsolver {
   };
 
   msf_pnp_params Params(int its, int max_records) const {
-    msf_pnp_params prm;
-    std::memset(&prm, 0, sizeof prm);
-    prm.struct_size = sizeof prm;
+    msf_pnp_params prm = sized<msf_pnp_params>();
     prm.fx = fx_, prm.fy = fy_, prm.cx = cx_, prm.cy = cy_;
     prm.th2 = th2_;
     prm.min_inliers = floor_;
@@ -253,9 +225,7 @@ class PnPsolver {
       std::vector<uint8_t> ib(static_cast<size_t>(max_records) * n_), ir(static_cast<size_t>(max_records) * n_);
       int32_t n_records = 0;
       const msf_pnp_params prm = Params(its, max_records);
-      msf_pnp_result out;
-      std::memset(&out, 0, sizeof out);
-      out.struct_size = sizeof out;
+      msf_pnp_result out = sized<msf_pnp_result>();
       out.n_records = &n_records, out.counts = counts.data(), out.iteration = iteration.data();
       out.n_inliers = n_inliers.data(), out.n_refined = n_refined.data(), out.Tcw_best = tb.data();
       out.Tcw_refined = tr.data(), out.inliers_best = ib.data(), out.inliers_refined = ir.data();
@@ -263,19 +233,22 @@ class PnPsolver {
       if (rc == MSF_ERR_CAPACITY && max_records < (1 << 16)) continue;
       if (rc != MSF_OK) return false;
       records_.clear();
-      for (int r = 0; r < n_records; r++) {
-        records_.push_back(Record{iteration[r], n_inliers[r], n_refined[r], {}, {}, {}, {}});
-        Record& rec = records_.back();
-        std::memcpy(rec.Tcw_best, &tb[r * 12], 48);
-        std::memcpy(rec.Tcw_refined, &tr[r * 12], 48);
-        rec.inliers_best.assign(ib.begin() + static_cast<size_t>(r) * n_, ib.begin() + static_cast<size_t>(r + 1) * n_);
-        rec.inliers_refined.assign(ir.begin() + static_cast<size_t>(r) * n_, ir.begin() + static_cast<size_t>(r + 1) * n_);
-      }
+      for (int r = 0; r < n_records; r++) records_.push_back(RecordAt(out, r, n_));
       counts_.swap(counts);
       sets_.swap(sets);
       cached_ = its;
       return true;
     }
+  }
+
+  // record `at` of a result in host memory whose inlier rows have the stride `stride`
+  Record RecordAt(const msf_pnp_result& res, size_t at, size_t stride) const {
+    Record rec{res.iteration[at], res.n_inliers[at], res.n_refined[at], {}, {}, {}, {}};
+    std::memcpy(rec.Tcw_best, res.Tcw_best + at * 12, 48);
+    std::memcpy(rec.Tcw_refined, res.Tcw_refined + at * 12, 48);
+    rec.inliers_best.assign(res.inliers_best + at * stride, res.inliers_best + at * stride + n_);
+    rec.inliers_refined.assign(res.inliers_refined + at * stride, res.inliers_refined + at * stride + n_);
+    return rec;
   }
 
   size_t RecordOf(int it) const {

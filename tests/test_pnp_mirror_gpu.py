@@ -28,10 +28,15 @@ def _build(tmp_path):
     return exe
 
 
-def test_iterate_equals_the_replay(tmp_path):
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    return _build(tmp_path_factory.mktemp("pnp_mirror"))
+
+
+def _iterate_all(exe, tmp_path, scenes):
+    """Runs the program on `scenes` (one Prefetch) and holds every iterate call of every solver to the replay.
+    -> the calls by solver, how many solvers reached beyond their cache, how many succeeded twice"""
     from mono_slam_framework_amd.matcher import FeatureMatcher
-    exe = _build(tmp_path)
-    scenes = [pr.scene("base", 1), pr.scene("few", 1), pr.scene("wide", 3, 63), pr.scene("base", 2, 9)]
     f_in, f_out = str(tmp_path / "lists.bin"), str(tmp_path / "log.txt")
     with open(f_in, "wb") as f:
         f.write(np.int32(len(scenes)).tobytes())
@@ -71,6 +76,21 @@ def test_iterate_equals_the_replay(tmp_path):
         succeeded_twice += sum(c["ok"] for c in calls[s]) >= 2
         print("solver %d (N %d): %d calls, returns %s" % (s, n, len(calls[s]), [(c["ok"], c["n"], c["no_more"]) for c in calls[s]]))
     fm.close()
+    return calls, reached_beyond, succeeded_twice
+
+
+def test_iterate_equals_the_replay(exe, tmp_path):
+    """solvers of 96, 96, 63 and 9 correspondences and, between them, one of 3: too short for a minimum set, so no sets
+    are drawn for its row of the block and its list gives no records"""
+    scenes = [pr.scene("base", 1), pr.scene("few", 1), pr.scene("wide", 3, 63), pr.scene("base", 2, 3), pr.scene("base", 2, 9)]
+    calls, reached_beyond, succeeded_twice = _iterate_all(exe, tmp_path, scenes)
     assert succeeded_twice >= 1 and reached_beyond >= 1
     # 55 % outliers of 96 cannot reach the floor of 48: empty returns to the end; N = 9 is below its floor of 10
-    assert [c["ok"] for c in calls[1]] == [0] * len(calls[1]) and calls[1][-1]["no_more"] and calls[3][0]["no_more"]
+    assert [c["ok"] for c in calls[1]] == [0] * len(calls[1]) and calls[1][-1]["no_more"] and calls[4][0]["no_more"]
+    # N = 3: false with bNoMore at the first call, as for a solver that fills its own cache
+    assert [(c["ok"], c["n"], c["no_more"], c["size"]) for c in calls[3]] == [(0, 0, 1, 0)]
+
+
+def test_a_prefetch_of_one_solver(exe, tmp_path):
+    calls, _, _ = _iterate_all(exe, tmp_path, [pr.scene("base", 1)])
+    assert any(c["ok"] for c in calls[0])
