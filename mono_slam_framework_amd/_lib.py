@@ -1,4 +1,4 @@
-"""ctypes view of include/msf_abi.h, include/msf_initializer.h, include/msf_local_mapping.h, include/msf_pnp.h and include/msf_pose.h.  Loading fails loudly when libmsf.so is missing: there is no CPU fallback."""
+"""ctypes view of include/msf_abi.h, include/msf_initializer.h, include/msf_local_mapping.h, include/msf_pnp.h, include/msf_pose.h and include/msf_ba.h.  Loading fails loudly when libmsf.so is missing: there is no CPU fallback."""
 import ctypes as C
 import os
 
@@ -57,6 +57,9 @@ PNP_SYMBOLS = ["msf_pnp_version", "msf_pnp_ransac", "msf_pnp_ransac_device"]
 
 # every symbol include/msf_pose.h declares (again a header and a version of its own)
 POSE_SYMBOLS = ["msf_pose_version", "msf_pose_optimize", "msf_pose_optimize_device"]
+
+# every symbol include/msf_ba.h declares (again a header and a version of its own)
+BA_SYMBOLS = ["msf_ba_version", "msf_bundle_adjust", "msf_bundle_adjust_device"]
 
 
 class Config(C.Structure):
@@ -184,6 +187,43 @@ def pose_shapes(lists, cap):
     return {name: (lead[per] + tuple(cap if t == "cap" else t for t in tail), dt) for name, dt, per, tail in POSE_ARRAYS}
 
 
+class BaParams(C.Structure):
+    """msf_ba_params: the intrinsics and the schedule of up to two rounds"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("fx", C.c_float), ("fy", C.c_float),
+                ("cx", C.c_float), ("cy", C.c_float), ("n_rounds", C.c_int32), ("iterations", C.c_int32 * 2),
+                ("robust", C.c_int32 * 2), ("huber_delta2", C.c_double), ("chi2", C.c_double)]
+
+
+BA_SLOTS = 64
+BA_PROBLEM_DTYPE = np.dtype([("n_cams", "<i4"), ("n_points", "<i4"), ("n_edges", "<i4"), ("cam0", "<i4"), ("point0", "<i4"),
+                             ("edge0", "<i4")])
+# msf_ba_result's arrays in declaration order: name -> (dtype, per "problem" / "cam" / "point" / "edge" / "round" / "it" /
+# "it_cam" / "it_point", trailing shape)
+BA_ARRAYS = [("status", "int32", "problem", ()), ("cam_Tcw", "float32", "cam", (12,)), ("points", "float32", "point", (3,)),
+             ("outliers", "uint8", "edge", ()), ("cam_pose_f64", "float64", "cam", (12,)), ("points_f64", "float64", "point", (3,)),
+             ("round_flags", "uint8", "edge", (2,)), ("round_iterations", "int32", "round", ()),
+             ("it_trials", "int32", "it", ()), ("it_lambda_in", "float64", "it", ()), ("it_lambda_out", "float64", "it", ()),
+             ("it_cost_in", "float64", "it", ()), ("it_cost_out", "float64", "it", ()),
+             ("it_cam_in", "float64", "it_cam", (7,)), ("it_point_in", "float64", "it_point", (3,)),
+             ("it_cam_out", "float64", "it_cam", (7,)), ("it_point_out", "float64", "it_point", (3,)),
+             ("it_Hcc", "float64", "it_cam", (21,)), ("it_bc", "float64", "it_cam", (6,)),
+             ("it_Hpp", "float64", "it_point", (6,)), ("it_bp", "float64", "it_point", (3,))]
+
+
+class BaResult(C.Structure):
+    """msf_ba_result: host pointers for msf_bundle_adjust, device pointers for msf_bundle_adjust_device"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(a[0], C.c_void_p) for a in BA_ARRAYS]
+
+
+def ba_shapes(problems, cams, points, edges):
+    """-> {name: (shape, dtype name)} of msf_ba_result's arrays for a call of `problems` problems with `cams`, `points`
+    and `edges` rows in all.  A problem's block of a per-iteration array starts at row 64 * cam0 (64 * point0) of the
+    flat [64 * cams] ([64 * points]) rows and is [64][n_cams] ([64][n_points])."""
+    lead = {"problem": (problems,), "cam": (cams,), "point": (points,), "edge": (edges,), "round": (problems, 2),
+            "it": (problems, BA_SLOTS), "it_cam": (BA_SLOTS * cams,), "it_point": (BA_SLOTS * points,)}
+    return {name: (lead[per] + tuple(tail), dt) for name, dt, per, tail in BA_ARRAYS}
+
+
 VIEW_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4")])
 MATCH_DTYPE = np.dtype([("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4")])
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("response", "<f4"), ("angle", "<f4"),
@@ -248,6 +288,10 @@ def load():
     L.msf_pose_optimize.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(PoseParams), C.POINTER(PoseResult)]
     L.msf_pose_optimize_device.argtypes = [vp, i32, vp, vp, i32, vp, vp, i64, vp, i64, C.POINTER(PoseParams),
                                            C.POINTER(PoseResult), vp]
+    L.msf_ba_version.restype = C.c_int
+    L.msf_bundle_adjust.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, C.POINTER(BaParams), C.POINTER(BaResult)]
+    L.msf_bundle_adjust_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, vp,
+                                           C.POINTER(BaParams), C.POINTER(BaResult), vp]
     L.msf_render_match_image.argtypes = [vp, C.POINTER(Image), C.POINTER(Image), vp, i32, vp, vp, vp, i64]
     L.msf_weights_info.argtypes = [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(i64)]
     L.msf_convert_weights.argtypes = [C.c_char_p, C.c_char_p]

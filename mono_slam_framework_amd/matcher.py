@@ -530,6 +530,93 @@ class _Matcher:
                                                      mask_stride or 0, C.byref(prm), C.byref(res), stream))
         return d
 
+    @staticmethod
+    def _ba_params(K, schedule, huber_delta2, chi2):
+        fx, fy, cx, cy = K
+        n_rounds, its, robust = schedule
+        p = _lib.BaParams(struct_size=C.sizeof(_lib.BaParams), fx=fx, fy=fy, cx=cx, cy=cy, n_rounds=n_rounds,
+                          huber_delta2=huber_delta2, chi2=chi2)
+        p.iterations[0], p.iterations[1] = its
+        p.robust[0], p.robust[1] = robust
+        return p
+
+    def bundle_adjust(self, cam_Tcw, cam_fixed, points, edge_cam, edge_point, edge_obs, K, schedule=(2, (5, 10), (1, 0)),
+                      stop=None, huber_delta2=5.991, chi2=5.991, diagnostics=True):
+        """Optimizer::LocalBundleAdjustment (Optimizer.cc:336-574; the default schedule) or BundleAdjustment (:71-215;
+        schedule = (1, (nIterations, 0), (bRobust, 0))) on one problem: cam_Tcw f32 [n_cams, 12] (rows 0..2 of Tcw),
+        cam_fixed uint8 [n_cams], points f32 [n_points, 3], edge_cam / edge_point int32 [n_edges] sorted by point,
+        edge_obs f32 [n_edges, 2], K = (fx, fy, cx, cy), schedule = (n_rounds, (iterations, iterations), (robust,
+        robust)), stop None or an int (pbStopFlag as the call starts).  -> dict: status (the rounds run), cam_Tcw f32
+        [n_cams, 12], points f32 [n_points, 3], outliers uint8 [n_edges], cam_pose_f64, points_f64, round_flags
+        [n_edges, 2], round_iterations [2] and with `diagnostics` the per-iteration arrays of msf_ba_result as [64] /
+        [64, n_cams, ...] / [64, n_points, ...].  More than 64 free cameras: MsfError with code MSF_ERR_CAPACITY."""
+        tcw = np.ascontiguousarray(cam_Tcw, np.float32).reshape(-1, 12)
+        fixed = np.ascontiguousarray(cam_fixed, np.uint8).reshape(-1)
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        ec = np.ascontiguousarray(edge_cam, np.int32).reshape(-1)
+        ep = np.ascontiguousarray(edge_point, np.int32).reshape(-1)
+        obs = np.ascontiguousarray(edge_obs, np.float32).reshape(-1, 2)
+        nc, npt, ne = len(tcw), len(pts), len(ec)
+        assert len(fixed) == nc and len(ep) == ne and len(obs) == ne
+        d = {k: np.zeros(shape, dt) for k, (shape, dt) in _lib.ba_shapes(1, nc, npt, ne).items()}
+        if not diagnostics:
+            for name, _, per, _ in _lib.BA_ARRAYS:
+                if per.startswith("it"):
+                    del d[name]
+        res = _fill(_lib.BaResult(), d)
+        prm = self._ba_params(K, schedule, huber_delta2, chi2)
+        st = None if stop is None else np.array([stop], np.int32)
+        self._check(self._L.msf_bundle_adjust(self._h, nc, tcw.ctypes.data, fixed.ctypes.data, npt, pts.ctypes.data, ne,
+                                              ec.ctypes.data, ep.ctypes.data, obs.ctypes.data,
+                                              st.ctypes.data if st is not None else None, C.byref(prm), C.byref(res)))
+        out = dict(d)
+        out["status"] = int(d["status"][0])
+        out["round_iterations"] = d["round_iterations"][0]
+        for name, _, per, _ in _lib.BA_ARRAYS:
+            if name not in d:
+                continue
+            if per == "it":
+                out[name] = d[name][0]
+            elif per == "it_cam":
+                out[name] = d[name].reshape((_lib.BA_SLOTS, nc) + d[name].shape[1:])
+            elif per == "it_point":
+                out[name] = d[name].reshape((_lib.BA_SLOTS, npt) + d[name].shape[1:])
+        return out
+
+    def bundle_adjust_device(self, d_problems, d_cam_Tcw, d_cam_fixed, d_points, d_edge_cam, d_edge_point, d_edge_obs, K,
+                             schedule=(2, (5, 10), (1, 0)), max_free_cams=64, d_stop=None, huber_delta2=5.991, chi2=5.991,
+                             out=None, diagnostics=True, stream=None):
+        """The same for a batch in device memory: d_problems int32 [P, 6] (n_cams, n_points, n_edges, cam0, point0,
+        edge0; n_cams < 0: no valid problem), the camera, point and edge arrays concatenated (edge indices local to
+        their problem), d_stop None or an int32 tensor of one element.  -> dict of CUDA tensors named and shaped as
+        _lib.ba_shapes(P, cams, points, edges) says; without `diagnostics` no per-iteration arrays.  `out`: tensors to
+        write into instead of fresh zeros.  One launch, asynchronous on `stream` (None = handle stream + sync)."""
+        import torch
+        for t, dt in ((d_problems, torch.int32), (d_cam_Tcw, torch.float32), (d_cam_fixed, torch.uint8), (d_points, torch.float32),
+                      (d_edge_cam, torch.int32), (d_edge_point, torch.int32), (d_edge_obs, torch.float32)):
+            assert t.is_cuda and t.is_contiguous() and t.dtype == dt
+        P = d_problems.numel() // 6
+        cams, points, edges = d_cam_fixed.numel(), d_points.numel() // 3, d_edge_cam.numel()
+        assert d_cam_Tcw.numel() == cams * 12 and d_edge_point.numel() == edges and d_edge_obs.numel() == edges * 2
+        if d_stop is not None:
+            assert d_stop.is_cuda and d_stop.dtype == torch.int32 and d_stop.numel() == 1
+        d = out
+        if d is None:
+            z = _zeros_on(d_points.device)
+            d = {k: z(shape, dt) for k, (shape, dt) in _lib.ba_shapes(P, cams, points, edges).items()}
+            if not diagnostics:
+                for name, _, per, _ in _lib.BA_ARRAYS:
+                    if per.startswith("it"):
+                        del d[name]
+        res = _fill(_lib.BaResult(), d)
+        prm = self._ba_params(K, schedule, huber_delta2, chi2)
+        self._check(self._L.msf_bundle_adjust_device(self._h, P, d_problems.data_ptr(), d_cam_Tcw.data_ptr(),
+                                                     d_cam_fixed.data_ptr(), d_points.data_ptr(), d_edge_cam.data_ptr(),
+                                                     d_edge_point.data_ptr(), d_edge_obs.data_ptr(), cams, points, edges,
+                                                     max_free_cams, d_stop.data_ptr() if d_stop is not None else None,
+                                                     C.byref(prm), C.byref(res), stream))
+        return d
+
     def render_match_image(self, frame1, frame2, matches, has_mp1=None, has_mp2=None):
         """Tracking::CreateCurrentMatchImage (Tracking.cc:899-940) -> uint8 [H, 2W, 3]."""
         a, b = self._image(frame1), self._image(frame2)

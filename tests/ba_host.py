@@ -1,0 +1,62 @@
+"""The host build of csrc/ba_solve.h (tests/cpp/ba_solve_host.cpp) behind ctypes: g++ -ffp-contract=off, no GPU."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "mono_slam_framework_amd", "csrc")
+
+
+def build(directory, optimise="-O2"):
+    so = os.path.join(str(directory), "libba_solve_host.so")
+    subprocess.check_call(["g++", "-std=c++17", optimise, "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-I", CSRC,
+                           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "ba_solve_host.cpp"), "-o", so])
+    L = C.CDLL(so)
+    vp = C.c_void_p
+    L.ba_host_adjust.argtypes = [C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double,
+                                 C.c_int, vp]
+    L.ba_host_adjust.restype = C.c_int
+    return L
+
+
+def run(L, sc, schedule, stop=None, huber_delta2=5.991, chi2=5.991, max_free=64, diagnostics=True):
+    """-> the dict that _Matcher.bundle_adjust returns, computed on the host.  sc: a scene of tests/ba_ref.py;
+    schedule = (n_rounds, (it0, it1), (robust0, robust1))."""
+    from mono_slam_framework_amd import _lib
+    nc, npt, ne = len(sc["cam_Tcw"]), len(sc["points"]), len(sc["edge_cam"])
+    d = {k: np.zeros(shape, dt) for k, (shape, dt) in _lib.ba_shapes(1, nc, npt, ne).items()}
+    given = [a[0] for a in _lib.BA_ARRAYS if diagnostics or not a[0].startswith("it_")]
+    ptrs = (C.c_void_p * len(_lib.BA_ARRAYS))(*[d[a[0]].ctypes.data if a[0] in given and d[a[0]].size else None
+                                                for a in _lib.BA_ARRAYS])
+    ptrs[0] = d["status"].ctypes.data
+    tcw = np.ascontiguousarray(sc["cam_Tcw"], np.float32).reshape(-1, 12)
+    fixed = np.ascontiguousarray(sc["cam_fixed"], np.uint8)
+    pts = np.ascontiguousarray(sc["points"], np.float32)
+    ec, ep = np.ascontiguousarray(sc["edge_cam"], np.int32), np.ascontiguousarray(sc["edge_point"], np.int32)
+    obs = np.ascontiguousarray(sc["edge_obs"], np.float32)
+    k = np.ascontiguousarray(sc["K"], np.float32)
+    sched = np.array([schedule[0], schedule[1][0], schedule[1][1], schedule[2][0], schedule[2][1]], np.int32)
+    st = None if stop is None else np.array([stop], np.int32)
+    status = L.ba_host_adjust(nc, tcw.ctypes.data, fixed.ctypes.data, npt, pts.ctypes.data, ne, ec.ctypes.data,
+                              ep.ctypes.data, obs.ctypes.data, st.ctypes.data if st is not None else None, k.ctypes.data,
+                              sched.ctypes.data, huber_delta2, chi2, max_free, ptrs)
+    assert status != -2
+    return shape_result(d, nc, npt)
+
+
+def shape_result(d, nc, npt):
+    """the flat arrays of one problem as [64][n_cams] / [64][n_points] blocks, status as an int"""
+    out = dict(d)
+    out["status"] = int(d["status"][0])
+    out["round_iterations"] = d["round_iterations"][0]
+    for k, v in d.items():
+        if k.startswith("it_"):
+            if v.shape[0] == 64 * nc and k in ("it_cam_in", "it_cam_out", "it_Hcc", "it_bc"):
+                out[k] = v.reshape((64, nc) + v.shape[1:])
+            elif k in ("it_point_in", "it_point_out", "it_Hpp", "it_bp"):
+                out[k] = v.reshape((64, npt) + v.shape[1:])
+            else:
+                out[k] = v[0]
+    return out

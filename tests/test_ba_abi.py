@@ -1,0 +1,101 @@
+"""CPU: include/msf_ba.h -- plain C, every symbol it declares is exported by libmsf.so and listed in _lib.BA_SYMBOLS,
+none of them belongs to the five earlier headers (whose lists and versions stay what they are), the structs have the
+layout the ctypes view relies on, and a null handle is refused without a GPU."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INCLUDE = os.path.join(ROOT, "include")
+EARLIER = ("msf_abi.h", "msf_initializer.h", "msf_local_mapping.h", "msf_pnp.h", "msf_pose.h")
+
+
+def _declared(header):
+    hdr = open(os.path.join(INCLUDE, header)).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    return sorted(set(re.findall(r"\b(msf_[a-z_0-9]+)\s*\(", hdr)))
+
+
+def test_header_symbols_are_exported_and_new():
+    from mono_slam_framework_amd import _lib
+    L = _lib.load()
+    names = _declared("msf_ba.h")
+    assert names == sorted(_lib.BA_SYMBOLS) and len(names) == 3
+    earlier = (_lib.ABI_SYMBOLS + _lib.INITIALIZER_SYMBOLS + _lib.LOCAL_MAPPING_SYMBOLS + _lib.PNP_SYMBOLS
+               + _lib.POSE_SYMBOLS)
+    for n in names:
+        assert hasattr(L, n), n
+        assert n not in earlier
+        for h in EARLIER:
+            assert n not in _declared(h)
+    assert L.msf_ba_version() == 1
+    # the five earlier versions and symbol counts are unchanged
+    assert L.msf_abi_version() == 4 and L.msf_initializer_version() == 1 and L.msf_local_mapping_version() == 1
+    assert L.msf_pnp_version() == 1 and L.msf_pose_version() == 1
+    assert len(_lib.ABI_SYMBOLS) == 44 and len(_lib.INITIALIZER_SYMBOLS) == 3 and len(_lib.LOCAL_MAPPING_SYMBOLS) == 4
+    assert len(_lib.PNP_SYMBOLS) == 3 and len(_lib.POSE_SYMBOLS) == 3
+    assert _declared("msf_pose.h") == sorted(_lib.POSE_SYMBOLS) and _declared("msf_pnp.h") == sorted(_lib.PNP_SYMBOLS)
+
+
+def test_header_is_plain_c(tmp_path):
+    src = tmp_path / "t.c"
+    src.write_text('#include "msf_ba.h"\n'
+                   "int main(void){ msf_ba_params p; msf_ba_result r; msf_ba_problem d; p.struct_size = sizeof p; "
+                   "r.struct_size = sizeof r; d.n_cams = MSF_BA_MAX_FREE_CAMS; "
+                   "return (int)(p.struct_size + r.struct_size) + d.n_cams + MSF_BA_VERSION + MSF_BA_SLOTS; }\n")
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", "-I", INCLUDE, str(src)])
+
+
+def test_struct_layouts_match_ctypes(tmp_path):
+    from mono_slam_framework_amd import _lib
+    fields = [name for name, _, _, _ in _lib.BA_ARRAYS]
+    prm = ["fx", "n_rounds", "iterations", "robust", "huber_delta2", "chi2"]
+    src = tmp_path / "sizes.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "msf_ba.h"\n'
+                   'int main(void){ printf("%zu %zu %zu", sizeof(msf_ba_params), sizeof(msf_ba_result), sizeof(msf_ba_problem));\n'
+                   + "".join('printf(" %%zu", offsetof(msf_ba_params, %s));\n' % f for f in prm)
+                   + "".join('printf(" %%zu", offsetof(msf_ba_result, %s));\n' % f for f in fields)
+                   + "return 0; }\n")
+    exe = str(tmp_path / "sizes")
+    subprocess.check_call(["gcc", "-std=c99", "-I", INCLUDE, str(src), "-o", exe])
+    sizes = [int(x) for x in subprocess.check_output([exe]).split()]
+    P, R = _lib.BaParams, _lib.BaResult
+    assert sizes == ([C.sizeof(P), C.sizeof(R), _lib.BA_PROBLEM_DTYPE.itemsize] + [getattr(P, f).offset for f in prm]
+                     + [getattr(R, f).offset for f in fields])
+    assert C.sizeof(P) == 64 and C.sizeof(R) == 8 + 8 * len(fields) and len(fields) == 21
+    assert _lib.BA_PROBLEM_DTYPE.itemsize == 24
+
+
+def test_shapes():
+    from mono_slam_framework_amd import _lib
+    s = _lib.ba_shapes(3, 10, 50, 200)
+    assert s["status"] == ((3,), "int32") and s["outliers"] == ((200,), "uint8") and s["cam_Tcw"] == ((10, 12), "float32")
+    assert s["round_flags"] == ((200, 2), "uint8") and s["round_iterations"] == ((3, 2), "int32")
+    assert s["it_trials"] == ((3, 64), "int32") and s["it_Hcc"] == ((640, 21), "float64")
+    assert s["it_point_in"] == ((3200, 3), "float64") and s["points_f64"] == ((50, 3), "float64")
+
+
+def test_the_kernel_file_is_built_and_its_header_is_a_dependency():
+    from mono_slam_framework_amd import build
+    assert "ba_kernels.hip" in build.HIP_SOURCES
+    assert os.path.join(INCLUDE, "msf_ba.h") in build._deps()
+    entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
+    assert "_lib.BA_SYMBOLS" in entry
+
+
+def test_a_null_handle_is_refused():
+    from mono_slam_framework_amd import _lib
+    L = _lib.load()
+    prm, res = _lib.BaParams(), _lib.BaResult()
+    assert L.msf_bundle_adjust(None, 0, None, None, 0, None, 0, None, None, None, None, C.byref(prm), C.byref(res)) == _lib.MSF_ERR_INVALID_ARG
+    assert L.msf_bundle_adjust_device(None, 0, None, None, None, None, None, None, None, 0, 0, 0, 1, None, C.byref(prm),
+                                      C.byref(res), None) == _lib.MSF_ERR_INVALID_ARG
+
+
+def test_the_mirror_compiles_with_plain_gxx():
+    """csrc/hip_bundle_adjustment.h and its test program: syntax only, no GPU (the behaviour is in test_ba_mirror_gpu.py)"""
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    subprocess.check_call(["g++", "-std=c++14", "-Wall", "-Werror", "-fsyntax-only", "-I", INCLUDE,
+                           "-I", os.path.join(ROOT, "mono_slam_framework_amd", "csrc"), "-isystem", os.path.join(rocm, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "test_ba_mirror.cpp")])
