@@ -442,6 +442,24 @@ int msf_debug_loftr_backbone(msf_handle* h, int32_t n, const uint8_t* d_a, const
  * [0, 2*max_batch_pairs), n outside [0, 2048], a null pointer with n > 0.  Not timed by msf_stage_times. */
 int msf_debug_orb_set_features(msf_handle* h, int32_t slot, int32_t n, const msf_keypoint* kp, const uint8_t* desc);
 
+/* ORB: everything behind FAST -- retainBest(2N) by score, HarrisResponses, retainBest(N), ICAngles, blur, rBRIEF -- on
+ * candidates the caller supplies.  d_frames / strides / first_slot as msf_extract_device (n_frames >= 1).  counts: HOST
+ * int32 [n_frames][8], candidates per (frame, level); cands: HOST int32 triples (lx, ly, fast_score), the lists one after
+ * the other in (frame, level) order.  The pyramid of the frames is made, each list is written where a call of n_frames
+ * frames keeps the level's FAST candidates, and the launches of an extraction that follow FAST run unchanged, with the
+ * launch geometry of n_frames frames; form 0: the dense form of the first (256 threads per (frame, level), which also
+ * score what they keep), 1: the streaming form (one wave, Harris responses by a launch of its own).  Results through
+ * msf_debug_get (MSF_DBG_FAST_CANDS returns the lists, MSF_DBG_STAGE1 / _KEYPOINTS / _DESCRIPTORS what came of them);
+ * a frame over one of the capacities leaves a slot that a match call answers with n_out = -1.  Returns when the work
+ * is complete.  MSF_ERR_INVALID_ARG, with nothing enqueued and the slots as they were, for a LoFTR handle, n_frames < 1
+ * or a slot range outside [0, 2*max_batch_pairs), form not 0 or 1, frames as msf_extract_device refuses them, a count
+ * below 0 or above the list's capacity + 16 (per level max(4096, w h / 8) entries, rounded up to 16, in a call of
+ * fewer than 8 frames, and never more in a larger one; the kernels clamp a count above the capacity and flag the frame), a score outside [0, 255], a position outside
+ * [31, w - 32] x [31, h - 32] of its level -- the kernels' loads assume that rectangle -- or on a level without one.
+ * Not timed by msf_stage_times. */
+int msf_debug_orb_tail(msf_handle* h, int32_t n_frames, const uint8_t* d_frames, int64_t frame_stride, int64_t row_stride,
+                       int32_t first_slot, const int32_t* counts, const int32_t* cands, int32_t form);
+
 /* per-stage device time, measured with HIP events on the launch stream (needs MSF_FLAG_PROFILE): the SUM over the batch
  * calls since the previous query -- queried after every call it is that call's times; a caller that enqueues many calls
  * ahead of the device (nothing in the recording waits) queries once afterwards and divides by its call count.  The events

@@ -35,7 +35,7 @@ ABI_SYMBOLS = ["msf_abi_version", "msf_default_config", "msf_create", "msf_destr
                "msf_last_error", "msf_match_pair", "msf_match_batch", "msf_match_batch_device",
                "msf_extract_device", "msf_match_slots_device", "msf_pack_matches_device", "msf_debug_get",
                "msf_debug_loftr_head", "msf_debug_loftr_transformer", "msf_debug_loftr_backbone",
-               "msf_debug_orb_set_features",
+               "msf_debug_orb_set_features", "msf_debug_orb_tail",
                "msf_stage_times", "msf_set_mappoints", "msf_count_mappoint_matches_device",
                "msf_store_frame", "msf_match_one_to_many", "msf_check_hypotheses",
                "msf_find_models", "msf_find_models_device",
@@ -264,6 +264,7 @@ def load():
     L.msf_debug_loftr_transformer.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp]
     L.msf_debug_loftr_backbone.argtypes = [vp, i32, vp, vp, i64, i64, i32, vp, vp, vp]
     L.msf_debug_orb_set_features.argtypes = [vp, i32, i32, vp, vp]
+    L.msf_debug_orb_tail.argtypes = [vp, i32, vp, i64, i64, i32, vp, vp, i32]
     L.msf_set_mappoints.argtypes = [vp, i32, vp, i32]
     L.msf_count_mappoint_matches_device.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp]
     L.msf_store_frame.argtypes = [vp, i32, C.POINTER(Image)]

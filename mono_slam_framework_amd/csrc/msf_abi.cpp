@@ -1762,6 +1762,32 @@ int msf_debug_orb_set_features(msf_handle* h, int32_t slot, int32_t n, const msf
   });
 }
 
+int msf_debug_orb_tail(msf_handle* h, int32_t n_frames, const uint8_t* d_frames, int64_t frame_stride, int64_t row_stride,
+                       int32_t first_slot, const int32_t* counts, const int32_t* cands, int32_t form) {
+  return guarded(h, "msf_debug_orb_tail", [&]() -> int {
+    if (h->cfg.kind != MSF_KIND_ORB) return fail(h, MSF_ERR_INVALID_ARG, "msf_debug_orb_tail: not an ORB handle");
+    if (n_frames < 1 || !d_frames || !counts || first_slot < 0 ||
+        (long long)first_slot + n_frames > 2ll * h->cfg.max_batch_pairs)
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_debug_orb_tail: slot range outside [0, 2*max_batch_pairs), or no frames");
+    if (form != 0 && form != 1) return fail(h, MSF_ERR_INVALID_ARG, "msf_debug_orb_tail: form is 0 (dense) or 1 (streaming)");
+    if (!aligned16(d_frames, frame_stride, row_stride))
+      return fail(h, MSF_ERR_INVALID_ARG, "device frames must be 16-byte aligned with strides multiple of 16");
+    if (row_stride < h->cfg.image_width ||
+        (n_frames > 1 && frame_stride < row_stride * (long long)h->cfg.image_height))
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_debug_orb_tail: strides smaller than the frame");
+    // the kernels' loads assume what this checks: nothing is enqueued for lists that fail it
+    const std::string why = h->orb.tail_refusal(n_frames, counts, cands);
+    if (!why.empty()) return fail(h, MSF_ERR_INVALID_ARG, "msf_debug_orb_tail: " + why);
+    CallScope cs{h};
+    if (int rc = cs.enter()) return rc;
+    Drain drain{cs.st};   // the copies read the caller's arrays: never return with one in flight
+    msf::FrameSrc src{d_frames, d_frames, n_frames, first_slot, frame_stride, (int)row_stride};
+    HIP_TRY(h, "orb tail", h->orb.tail(src, n_frames, counts, cands, form, cs.st));
+    drain.armed = false;
+    return cs.finish();
+  });
+}
+
 int msf_stage_times(msf_handle* h, const char** names, float* ms, int32_t cap) {
   if (!names || !ms || cap < 1) return 0;
   const int n = guarded(h, "msf_stage_times", [&]() -> int {

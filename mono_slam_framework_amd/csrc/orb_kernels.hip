@@ -2470,8 +2470,6 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
   uint32_t* const d_cand_cnt_ = this->d_cand_cnt_ - back * kOrbLevels;
   uint2* const d_cmap_ = this->d_cmap_ - back * kOrbLevels;     // (its entries are absolute offsets into d_cand_ / d_cand_sc_)
   uint32_t* const d_qstat_ = this->d_qstat_ - back * kOrbLevels * kQStat;
-  uint32_t* const d_s1_cnt_ = this->d_s1_cnt_ - back * kOrbLevels;
-  uint4* const d_s1_ = this->d_s1_ - back * g.s1_total;
   uint32_t* const d_redo_hist_ = this->d_redo_hist_ - back * kOrbLevels * 256;
   uint32_t* const d_redo_thr_ = this->d_redo_thr_ - back * kOrbLevels;
   if ((e = hipMemsetAsync(this->d_cand_cnt_, 0, (size_t)n * kOrbLevels * 4, st))) return e;
@@ -2483,7 +2481,7 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
   // A call of a few frames (the single-pair MatchFrames, a key frame upload) is latency-bound: a wave of the
   // streaming pass walks its strip in ~90 dependent steps, whereas the dense tile kernel is one short workgroup per
   // tile.  Such calls take k_resize + the dense kernel directly; the result is the same either way.
-  const int force_tau = (force_tau_ == 0 && n < stream_min_frames_) ? kFastT : force_tau_;
+  const int force_tau = call_force_tau(n);
   const bool dense = force_tau == kFastT;
   // where each (frame, level)'s candidate list lives in this call (k_cand_reset): its primary list, or -- a dense call --
   // the frame's full-capacity region in the pool
@@ -2492,24 +2490,6 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
   const int dyn = (fast_two_part_ && force_tau == 0) ? 1 : 0;
   bool fused = fused_ && !dense && g.total_tiles > 0;
   for (int l = 1; l < g.nlevels; l++) fused = fused && g.lv[l].wk_fused != 0;
-  auto launch_resize = [&](int l) {
-    const OrbLevelInfo& L = g.lv[l];
-    // band height: 8 output rows x 256 threads measured best (rth 4: 3.26 ms, 8: 2.71, 12: 2.77, 16: 2.74 per 2048
-    // [r02, table-driven kernel: 12 or 16 rows on the small levels only: 2.65 vs 2.65-2.73, within run-to-run noise]
-    // 720p frames; workgroup sizes chosen to fill whole passes of 4 px x 4 row tasks -- 320..512 threads -- were
-    // slower, 2.99: more, smaller workgroups hide the stage-then-compute latency better than full lanes do)
-    const int sw16 = (g.lv[l - 1].w + 16 + 15) & ~15;
-    const int groups = (L.w + 3) >> 2;
-    int rth = 8;
-    const int threads = 256;
-    while (rth > 4 && ((rth * 5 + 3) / 4 + 3) * sw16 > 60000) rth -= 4;
-    const int lds_rows = (rth * 5 + 3) / 4 + 3;
-    const uint32_t magic_n16 = (uint32_t)(0x100000000ull / (uint32_t)(sw16 >> 4)) + 1u;
-    const uint32_t magic_groups = groups > 1 ? (uint32_t)(0x100000000ull / (uint32_t)groups) + 1u : 0u;
-    hipLaunchKernelGGL(resize_shared_[l] ? k_resize<true> : k_resize<false>, dim3((L.h + rth - 1) / rth, n), dim3(threads),
-                       (size_t)lds_rows * sw16 + 8 * kResizeMaxRows, st, g, src, d_pyr_, d_tab_, l, rth, lds_rows, magic_n16,
-                       magic_groups);
-  };
   // the units of levels [l_lo, l_hi]: per XCD ceil(n / 8) frames x (1 threshold unit + the level's strips), see k_walk
   auto launch_walk = [&](int l_lo, int l_hi, int chain, int resize_mask, int predict_pct) {
     long long per_frame = 0;
@@ -2543,7 +2523,7 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
     hipMemcpyAsync(h_walk_abort_, d_walk_abort_, 8, hipMemcpyDeviceToHost, st);
     if (evs) hipEventRecord(evs[1], st);
   } else {
-    for (int l = 1; l < g.nlevels; l++) launch_resize(l);
+    for (int l = 1; l < g.nlevels; l++) launch_resize(src, n, l, st);
     if (evs) hipEventRecord(evs[1], st);
     if (g.total_tiles > 0) {
       if (dense) {   // MSF_FLAG_FAST_DENSE / a call of a few frames: the plain detector over every tile, nothing to verify
@@ -2575,6 +2555,39 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
                        g.max_level_tiles, d_cand_cnt_, d_cand_, d_cand_sc_, d_cmap_, (uint32_t*)nullptr, d_redo_thr_);
   }
   if (evs) hipEventRecord(evs[2], st);
+  launch_tail(src, n, dense, st, evs);
+  return hipGetLastError();
+}
+
+void OrbPipeline::launch_resize(const FrameSrc& src, int n, int l, hipStream_t st) {
+  const OrbGeometry& g = g_;
+  uint8_t* const d_pyr_ = this->d_pyr_ - (ptrdiff_t)src.slot0 * g.pyr_bytes;   // work rows: see extract_range
+  const OrbLevelInfo& L = g.lv[l];
+  // band height: 8 output rows x 256 threads measured best (rth 4: 3.26 ms, 8: 2.71, 12: 2.77, 16: 2.74 per 2048
+  // [r02, table-driven kernel: 12 or 16 rows on the small levels only: 2.65 vs 2.65-2.73, within run-to-run noise]
+  // 720p frames; workgroup sizes chosen to fill whole passes of 4 px x 4 row tasks -- 320..512 threads -- were
+  // slower, 2.99: more, smaller workgroups hide the stage-then-compute latency better than full lanes do)
+  const int sw16 = (g.lv[l - 1].w + 16 + 15) & ~15;
+  const int groups = (L.w + 3) >> 2;
+  int rth = 8;
+  const int threads = 256;
+  while (rth > 4 && ((rth * 5 + 3) / 4 + 3) * sw16 > 60000) rth -= 4;
+  const int lds_rows = (rth * 5 + 3) / 4 + 3;
+  const uint32_t magic_n16 = (uint32_t)(0x100000000ull / (uint32_t)(sw16 >> 4)) + 1u;
+  const uint32_t magic_groups = groups > 1 ? (uint32_t)(0x100000000ull / (uint32_t)groups) + 1u : 0u;
+  hipLaunchKernelGGL(resize_shared_[l] ? k_resize<true> : k_resize<false>, dim3((L.h + rth - 1) / rth, n), dim3(threads),
+                     (size_t)lds_rows * sw16 + 8 * kResizeMaxRows, st, g, src, d_pyr_, d_tab_, l, rth, lds_rows, magic_n16,
+                     magic_groups);
+}
+
+void OrbPipeline::launch_tail(const FrameSrc& src, int n, bool dense, hipStream_t st, hipEvent_t* evs) {
+  const OrbGeometry& g = g_;
+  const ptrdiff_t back = (ptrdiff_t)src.slot0;                 // work rows: see extract_range
+  uint8_t* const d_pyr_ = this->d_pyr_ - back * g.pyr_bytes;
+  uint32_t* const d_cand_cnt_ = this->d_cand_cnt_ - back * kOrbLevels;
+  uint2* const d_cmap_ = this->d_cmap_ - back * kOrbLevels;
+  uint32_t* const d_s1_cnt_ = this->d_s1_cnt_ - back * kOrbLevels;
+  uint4* const d_s1_ = this->d_s1_ - back * g.s1_total;
   hipLaunchKernelGGL(k_thr_harris, dim3(g.nlevels, n), dim3(dense ? 256 : 64), 0, st, g, src, d_pyr_,
                      d_cand_cnt_, d_cand_, d_cand_sc_, d_cmap_, d_s1_cnt_, d_s1_, d_status_, dense ? 1 : 0);
   if (!dense) {
@@ -2594,7 +2607,64 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
     hipLaunchKernelGGL(kd, dim3(bx, n), dim3(256), 0, st, g, src, d_pyr_, d_kp_, d_kp_cnt_, d_desc_);
   }
   if (evs) hipEventRecord(evs[4], st);
-  return hipGetLastError();
+}
+
+std::string OrbPipeline::tail_refusal(int n, const int32_t* counts, const int32_t* cands) const {
+  if (n < 1 || n > work_frames_) return "n_frames outside [1, 2*max_batch_pairs]";
+  const bool dense = call_force_tau(n) == kFastT;
+  int cap[kOrbLevels];
+  for (int l = 0; l < kOrbLevels; l++) cap[l] = l < g_.nlevels ? (dense ? g_.lv[l].cand_cap : prim_.cap[l]) : 0;
+  return check_tail_lists(g_, cap, n, counts, cands);
+}
+
+hipError_t OrbPipeline::tail(const FrameSrc& src, int n, const int32_t* counts, const int32_t* cands, int form,
+                             hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (src.slot0 < 0 || src.slot0 + n > max_slots_ || n > work_frames_) return hipErrorInvalidValue;
+  const OrbGeometry& g = g_;
+  const bool dense = call_force_tau(n) == kFastT;
+  if (dense && (long long)n * g.cand_total > (long long)g.pool_entries) return hipErrorInvalidValue;
+  last_src_ = src;
+  last_n_ = n;
+  last_fused_ = false;
+  last_dense_ = true;      // MSF_DBG_FAST_CANDS returns the lists as they stand
+  hipError_t e;
+  if ((e = hipMemsetAsync(d_status_ + src.slot0, 0, (size_t)n * 4, st))) return e;
+  hipLaunchKernelGGL(k_cand_reset, dim3((n * kOrbLevels + 255) / 256), dim3(256), 0, st, g, prim_, this->d_cmap_, n, dense ? 1 : 0);
+  hipLaunchKernelGGL(k_fill_u32, dim3((n * kOrbLevels + 255) / 256), dim3(256), 0, st, d_tau_,
+                     d_tau_ + (size_t)work_frames_ * kOrbLevels, (uint32_t)kFastT, n * kOrbLevels);
+  for (int l = 1; l < g.nlevels; l++) launch_resize(src, n, l, st);
+  // the lists go where k_cand_reset has just put them: asked of the device, not restated here
+  std::vector<uint2> cmap((size_t)n * kOrbLevels);
+  if ((e = hipMemcpyAsync(cmap.data(), this->d_cmap_, cmap.size() * sizeof(uint2), hipMemcpyDeviceToHost, st))) return e;
+  if ((e = hipStreamSynchronize(st))) return e;
+  size_t total = 0;
+  for (int i = 0; i < n * kOrbLevels; i++) total += (size_t)counts[i];
+  std::vector<uint32_t> keys(total ? total : 1), cnt((size_t)n * kOrbLevels);
+  std::vector<uint8_t> scs(total ? total : 1);
+  for (size_t i = 0; i < total; i++) {
+    keys[i] = (uint32_t)cands[3 * i] | (uint32_t)cands[3 * i + 1] << 16;
+    scs[i] = (uint8_t)cands[3 * i + 2];
+  }
+  size_t off = 0;
+  for (int i = 0; i < n * kOrbLevels; i++) {
+    cnt[i] = (uint32_t)counts[i];
+    // a count above the capacity (tail_refusal allows kTailCountMargin more) stays in the count word -- k_thr_harris clamps
+    // and flags it --, and only what fits is written
+    const size_t m = std::min<size_t>(cnt[i], cmap[i].y);
+    if (m) {
+      if ((e = hipMemcpyAsync(d_cand_ + (size_t)cmap[i].x, keys.data() + off, m * 4, hipMemcpyHostToDevice, st))) break;
+      if ((e = hipMemcpyAsync(d_cand_sc_ + (size_t)cmap[i].x, scs.data() + off, m, hipMemcpyHostToDevice, st))) break;
+    }
+    off += cnt[i];
+  }
+  if (!e) e = hipMemcpyAsync(this->d_cand_cnt_, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice, st);
+  if (!e) {
+    launch_tail(src, n, form == 0, st, nullptr);
+    e = hipGetLastError();
+  }
+  const hipError_t es = hipStreamSynchronize(st);     // the copies read this call's host arrays
+  return e ? e : es;
 }
 
 // the train chunk in effect: kTrainChunk, or MSF_ORB_TRAIN_CHUNK in [16, kTrainChunk] (read once per process)

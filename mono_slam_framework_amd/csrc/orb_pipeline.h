@@ -60,6 +60,14 @@ class OrbPipeline {
   // debug (msf_debug_orb_set_features): n <= kKpCap caller features (HOST pointers) into feature slot `slot`, its count
   // set to n and its status word cleared; enqueued on `st`, the caller waits before kp / desc go away
   hipError_t set_features(int slot, int n, const msf_keypoint* kp, const uint8_t* desc, hipStream_t st);
+  // debug (msf_debug_orb_tail): everything behind FAST on candidates the caller supplies.  The pyramid of the n frames
+  // is made (k_resize), the lists of (frame, level) -- counts [n][8], cands (lx, ly, score) triples in (frame, level)
+  // order, HOST pointers -- are written where a call of n frames keeps them, and launch_tail() runs on them: form 0 the
+  // dense form (k_thr_harris with 256 threads scores the kept candidates itself), 1 the streaming form (one wave, then
+  // k_harris_flat).  The caller has checked the lists with tail_refusal(); returns with the stream drained.
+  hipError_t tail(const FrameSrc& src, int n, const int32_t* counts, const int32_t* cands, int form, hipStream_t st);
+  // why tail() may not take these lists (check_tail_lists, orb_plan.h), or empty
+  std::string tail_refusal(int n, const int32_t* counts, const int32_t* cands) const;
 
   const OrbGeometry& geom() const { return g_; }
   int max_slots() const { return max_slots_; }
@@ -139,6 +147,12 @@ class OrbPipeline {
   bool last_dense_ = false;        // the last extraction was a dense call (no streaming pass, no dense-pass queue)
   void read_env();                 // the MSF_ORB_* overrides (tests), all in one place
   hipError_t extract_range(const FrameSrc& src, int n, hipStream_t st, hipEvent_t* evs);
+  // a call of n frames is dense (k_resize + the tile kernel, lists in the pool) when this is kFastT
+  int call_force_tau(int n) const { return (force_tau_ == 0 && n < stream_min_frames_) ? kFastT : force_tau_; }
+  void launch_resize(const FrameSrc& src, int n, int l, hipStream_t st);
+  // selection and description of n frames whose candidate lists are complete: k_thr_harris (dense_form: 256 threads,
+  // scoring what it keeps; else one wave + k_harris_flat), k_select, k_describe; evs as extract_range (3 and 4 recorded)
+  void launch_tail(const FrameSrc& src, int n, bool dense_form, hipStream_t st, hipEvent_t* evs);
 };
 
 }  // namespace msf

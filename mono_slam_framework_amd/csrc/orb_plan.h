@@ -392,4 +392,35 @@ inline std::string plan_orb(const OrbPlanRequest& rq, OrbPlan* out) {
   return "";
 }
 
+// msf_debug_orb_tail: the caller's candidate lists -- counts [n][kOrbLevels], cands (lx, ly, score) triples in
+// (frame, level) order -- against what the kernels behind FAST take for granted; cap[l] is the capacity of level l's
+// list in a call of n frames.  Returns why the lists are refused, or an empty string.
+//  * a count may exceed the capacity by kTailCountMargin: k_thr_harris clamps such a count itself and flags the frame
+//    (the entries past the capacity are not written anywhere);
+//  * every position lies in [kEdge, w - kEdge - 1] x [kEdge, h - kEdge - 1]: harris_at reads 12 aligned bytes around
+//    x - 4 .. x + 4 and k_describe 48 around x - 22 .. x + 22 without a bounds check -- FAST never lists a corner
+//    outside that rectangle, so the rectangle is the kernels' precondition.
+constexpr int kTailCountMargin = 16;
+inline std::string check_tail_lists(const OrbGeometry& g, const int* cap, int n, const int32_t* counts,
+                                    const int32_t* cands) {
+  if (n < 1 || !counts) return "no frames, or null counts";
+  size_t at = 0;
+  for (int f = 0; f < n; f++)
+    for (int l = 0; l < kOrbLevels; l++) {
+      const long long c = counts[f * kOrbLevels + l];
+      if (c == 0) continue;
+      if (l >= g.nlevels || c < 0 || c > (long long)cap[l] + kTailCountMargin) return "count outside [0, capacity + 16]";
+      if (!cands) return "null candidates with a count > 0";
+      const OrbLevelInfo& L = g.lv[l];
+      if (L.w <= 2 * kEdge || L.h <= 2 * kEdge) return "candidates on a level without a key point rectangle";
+      for (long long i = 0; i < c; i++, at++) {
+        const int32_t x = cands[3 * at], y = cands[3 * at + 1], s = cands[3 * at + 2];
+        if (x < kEdge || x > L.w - kEdge - 1 || y < kEdge || y > L.h - kEdge - 1)
+          return "position outside [31, w - 32] x [31, h - 32] of its level";
+        if (s < 0 || s > 255) return "score outside [0, 255]";
+      }
+    }
+  return "";
+}
+
 }  // namespace msf

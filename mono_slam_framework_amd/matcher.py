@@ -737,6 +737,26 @@ class FeatureMatcher(_Matcher):
         self._check(self._L.msf_debug_orb_set_features(self._h, slot, len(kp), kp.ctypes.data if len(kp) else None,
                                                        desc.ctypes.data if len(kp) else None))
 
+    def orb_tail(self, d_frames, lists, first_slot=0, form=0):
+        """Debug (msf_debug_orb_tail): everything behind FAST on the caller's candidates.  d_frames: device uint8
+        [n, H, pitch]; lists[f][l]: int [k, 3] rows (lx, ly, fast_score) of frame f, level l (missing levels: empty);
+        form 0: the dense form of k_thr_harris, 1: the streaming form + k_harris_flat.  Results: stage1 / keypoints /
+        descriptors(first_slot + f, cache=True)."""
+        n = d_frames.shape[0]
+        if len(lists) != n:
+            raise ValueError("one list of levels per frame")
+        counts = np.zeros((n, 8), np.int32)
+        rows = []
+        for f, levels in enumerate(lists):
+            for l, c in enumerate(levels):
+                c = np.asarray(c, np.int32).reshape(-1, 3)
+                counts[f, l] = len(c)
+                rows.append(c)
+        cands = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 3), np.int32))
+        self._check(self._L.msf_debug_orb_tail(self._h, n, d_frames.data_ptr(), d_frames.stride(0), d_frames.stride(1),
+                                               first_slot, counts.ctypes.data, cands.ctypes.data if len(cands) else None,
+                                               form))
+
     def match_form(self):
         """(form, chunk): the kernel of this handle's last match launch -- 0 none yet, 1 k_match_split (calls of at most
         128 pairs), 2 k_match -- and the train chunk in effect (1024, or MSF_ORB_TRAIN_CHUNK)."""

@@ -7,6 +7,7 @@
 //   orb_plan sweep K N              (part K of N of) every width 64..8192 at height 64 and every height 64..8192 at width 64, both
 //                                   level-size modes, max_slots 2 and 256: the flags, and what the kernels rely on
 //                                   re-derived from the tables themselves; failures to stderr and the exit status
+//   orb_plan tail_lists W H         check_tail_lists (the host check of msf_debug_orb_tail) on every level of a W x H plan
 // Fields are printed, not struct bytes: padding is no part of the contract.
 #include <cstdio>
 #include <cstdlib>
@@ -237,10 +238,63 @@ int sweep(int k, int n) {
   return failures ? 1 : 0;
 }
 
+// check_tail_lists (msf_debug_orb_tail's host check) on every level of a w x h plan: the rectangle's corners pass, one
+// step outside any edge is refused, and so are levels without a rectangle, counts and scores out of range.  The lists
+// are sized exactly, so a read past a list's end is the sanitizer's to report.
+int tail_lists(int w, int h) {
+  OrbPlan p;
+  const std::string err = plan_orb(request(w, h, 4, false), &p);
+  CHECK(err.empty(), "%d x %d: %s", w, h, err.c_str());
+  if (!err.empty()) return 1;
+  const OrbGeometry& g = p.g;
+  int cap[kOrbLevels];
+  for (int l = 0; l < kOrbLevels; l++) cap[l] = g.lv[l].cand_cap;
+  auto one = [&](int l, int x, int y, int s) {
+    std::vector<int32_t> counts(2 * kOrbLevels, 0), c = {x, y, s};
+    counts[kOrbLevels + l] = 1;                       // the second of two frames
+    return check_tail_lists(g, cap, 2, counts.data(), c.data());
+  };
+  int with_rect = 0;
+  for (int l = 0; l < kOrbLevels; l++) {
+    const OrbLevelInfo& L = g.lv[l];
+    const int x1 = L.w - kEdge - 1, y1 = L.h - kEdge - 1;
+    if (x1 < kEdge || y1 < kEdge) {
+      CHECK(!one(l, kEdge, kEdge, 50).empty(), "level %d has no rectangle", l);
+      continue;
+    }
+    with_rect++;
+    for (int x : {kEdge, x1})
+      for (int y : {kEdge, y1}) CHECK(one(l, x, y, 0).empty() && one(l, x, y, 255).empty(), "level %d corner %d %d", l, x, y);
+    CHECK(!one(l, kEdge - 1, kEdge, 50).empty() && !one(l, x1 + 1, kEdge, 50).empty(), "level %d x outside", l);
+    CHECK(!one(l, kEdge, kEdge - 1, 50).empty() && !one(l, kEdge, y1 + 1, 50).empty(), "level %d y outside", l);
+    CHECK(!one(l, -kEdge, kEdge, 50).empty() && !one(l, kEdge, 1 << 20, 50).empty(), "level %d far outside", l);
+    CHECK(!one(l, kEdge, kEdge, 256).empty() && !one(l, kEdge, kEdge, -1).empty(), "level %d score", l);
+    std::vector<int32_t> counts(kOrbLevels, 0), c;
+    counts[l] = cap[l] + kTailCountMargin;
+    for (int i = 0; i < counts[l]; i++) { c.push_back(kEdge + i % (x1 - kEdge + 1)); c.push_back(y1); c.push_back(i & 255); }
+    CHECK(check_tail_lists(g, cap, 1, counts.data(), c.data()).empty(), "level %d count = capacity + margin", l);
+    c[3 * (counts[l] - 1)] = x1 + 1;                  // only the last entry is bad
+    CHECK(!check_tail_lists(g, cap, 1, counts.data(), c.data()).empty(), "level %d last entry", l);
+    counts[l]++;
+    CHECK(!check_tail_lists(g, cap, 1, counts.data(), c.data()).empty(), "level %d count above the margin", l);
+    counts[l] = -1;
+    CHECK(!check_tail_lists(g, cap, 1, counts.data(), c.data()).empty(), "level %d negative count", l);
+    counts[l] = 1;
+    CHECK(!check_tail_lists(g, cap, 1, counts.data(), nullptr).empty(), "level %d null candidates", l);
+  }
+  std::vector<int32_t> none(kOrbLevels, 0);
+  CHECK(check_tail_lists(g, cap, 1, none.data(), nullptr).empty(), "%s", "empty lists");
+  CHECK(!check_tail_lists(g, cap, 0, none.data(), nullptr).empty() && !check_tail_lists(g, cap, 1, nullptr, nullptr).empty(),
+        "%s", "no frames / null counts");
+  std::printf("tail_lists %d x %d: levels_with_rectangle=%d failures=%d\n", w, h, with_rect, failures);
+  return failures ? 1 : 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc == 4 && !std::strcmp(argv[1], "sweep") && std::atoi(argv[3]) > 0) return sweep(std::atoi(argv[2]), std::atoi(argv[3]));
+  if (argc == 4 && !std::strcmp(argv[1], "tail_lists")) return tail_lists(std::atoi(argv[2]), std::atoi(argv[3]));
   std::vector<OrbPlanRequest> reqs;
   if (argc == 2 && !std::strcmp(argv[1], "golden")) {
     reqs = golden_requests();

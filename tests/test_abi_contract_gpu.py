@@ -98,6 +98,7 @@ def test_null_handle(orb):
         "msf_debug_loftr_transformer": lambda: L.msf_debug_loftr_transformer(z, 1, 0, 8, z, z, z, z, z),
         "msf_debug_loftr_backbone": lambda: L.msf_debug_loftr_backbone(z, 1, z, z, 0, 0, 0, z, z, z),
         "msf_debug_orb_set_features": lambda: L.msf_debug_orb_set_features(z, 0, 0, z, z),
+        "msf_debug_orb_tail": lambda: L.msf_debug_orb_tail(z, 1, z, 0, 0, 0, z, z, 0),
         "msf_set_mappoints": lambda: L.msf_set_mappoints(z, 0, z, 0),
         "msf_count_mappoint_matches_device": lambda: L.msf_count_mappoint_matches_device(z, 1, z, 16, z, z, z, z, z),
         "msf_store_frame": lambda: L.msf_store_frame(z, 0, None),
@@ -175,6 +176,9 @@ def test_bad_arguments_and_the_call_after(orb, loftr, frames):
     fd = np.arange(4 * 32, dtype=np.uint8).reshape(4, 32)
     pk, pd = fk.ctypes.data, fd.ctypes.data
     set_features = "msf_debug_orb_set_features"
+    tail = "msf_debug_orb_tail"
+    tc = np.array([[1, 0, 0, 0, 0, 0, 0, 0]], np.int32)                       # one candidate on level 0
+    tl, tb = np.array([[100, 100, 50]], np.int32), np.array([[30, 100, 50]], np.int32)
 
     def good_set_features():
         orb.set_features(2 * P - 1, fk, fd)                  # the last caller slot
@@ -217,6 +221,7 @@ def test_bad_arguments_and_the_call_after(orb, loftr, frames):
         "msf_debug_loftr_transformer": lambda: loftr.transformer_device(feat[0], feat[1], feat_o[0], feat_o[1], 0, 2),
         "msf_debug_loftr_backbone": lambda: loftr.backbone_device(ld[0], ld[1], tok[0], tok[1], act_image=3),
         set_features: good_set_features,
+        tail: lambda: (orb.orb_tail(d[0][:1], [[tl]], first_slot=1), orb.keypoints(1, cache=True)),
     }
     bad_arg = lambda e: e + ": bad argument"                                                     # noqa: E731
     # (handle, entry whose good call follows, what is wrong, call, status, text left in msf_last_error)
@@ -310,6 +315,12 @@ def test_bad_arguments_and_the_call_after(orb, loftr, frames):
          INV, set_features + ": null pointer with n > 0"),
         (orb, set_features, "null descriptors with n > 0", lambda: L.msf_debug_orb_set_features(h, 0, 4, pk, None),
          INV, set_features + ": null pointer with n > 0"),
+        (loftr, tail, "LoFTR handle", lambda: L.msf_debug_orb_tail(lh, 1, dA, fs, PITCH, 0, tc.ctypes.data, tl.ctypes.data, 0),
+         INV, tail + ": not an ORB handle"),
+        (orb, tail, "x = 30", lambda: L.msf_debug_orb_tail(h, 1, dA, fs, PITCH, 0, tc.ctypes.data, tb.ctypes.data, 0),
+         INV, tail + ": position outside [31, w - 32] x [31, h - 32] of its level"),
+        (orb, tail, "form = 2", lambda: L.msf_debug_orb_tail(h, 1, dA, fs, PITCH, 0, tc.ctypes.data, tl.ctypes.data, 2),
+         INV, tail + ": form is 0 (dense) or 1 (streaming)"),
         (loftr, "loftr msf_match_batch_device", "n_pairs > max_batch_pairs",
          lambda: L.msf_match_batch_device(lh, P + 1, ld[0].data_ptr(), ld[1].data_ptr(), 640 * 480, 640, lo.data_ptr(), 64,
                                           ln.data_ptr(), None), INV, "n_pairs exceeds max_batch_pairs"),

@@ -58,6 +58,14 @@ def test_header_needs_no_hip():
                    input='#include "orb_plan.h"\n', text=True, check=True)
 
 
+@pytest.mark.parametrize("size,levels", [((192, 144), 5), ((333, 257), 8), ((76, 64), 1), ((100, 92), 3)])
+def test_tail_list_check_in_a_sanitized_executable(sanitized, size, levels):
+    """check_tail_lists, the host check in front of msf_debug_orb_tail, at the sizes tests/test_orb_tail_gpu.py uses: the
+    rectangle's corners pass, one step outside is refused on every level, lists are read to their end and no further"""
+    out = _run([sanitized, "tail_lists", str(size[0]), str(size[1])])
+    assert out == ["tail_lists %d x %d: levels_with_rectangle=%d failures=0" % (size[0], size[1], levels)]
+
+
 def test_golden_plans_in_a_sanitized_executable(sanitized):
     """every scalar of OrbGeometry, every member of each OrbLevelInfo, the primary lists, resize_shared, umax, the
     Harris units, length and FNV-1a 64 of the tables and of the disc: as recorded from the code init held before"""

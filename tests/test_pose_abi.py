@@ -31,7 +31,7 @@ def test_header_symbols_are_exported_and_new():
     assert L.msf_pose_version() == 1
     assert L.msf_abi_version() == 4 and L.msf_initializer_version() == 1 and L.msf_local_mapping_version() == 1
     assert L.msf_pnp_version() == 1
-    assert len(_lib.ABI_SYMBOLS) == 44 and len(_lib.INITIALIZER_SYMBOLS) == 3 and len(_lib.LOCAL_MAPPING_SYMBOLS) == 4
+    assert len(_lib.ABI_SYMBOLS) == 45 and len(_lib.INITIALIZER_SYMBOLS) == 3 and len(_lib.LOCAL_MAPPING_SYMBOLS) == 4
     assert len(_lib.PNP_SYMBOLS) == 3 and _declared("msf_pnp.h") == sorted(_lib.PNP_SYMBOLS)
 
 
