@@ -1,4 +1,4 @@
-"""ctypes view of include/msf_abi.h, include/msf_initializer.h, include/msf_local_mapping.h, include/msf_pnp.h, include/msf_pose.h and include/msf_ba.h.  Loading fails loudly when libmsf.so is missing: there is no CPU fallback."""
+"""ctypes view of include/msf_abi.h, include/msf_initializer.h, include/msf_local_mapping.h, include/msf_pnp.h, include/msf_pose.h, include/msf_ba.h and include/msf_global_ba.h.  Loading fails loudly when libmsf.so is missing: there is no CPU fallback."""
 import ctypes as C
 import os
 
@@ -60,6 +60,11 @@ POSE_SYMBOLS = ["msf_pose_version", "msf_pose_optimize", "msf_pose_optimize_devi
 
 # every symbol include/msf_ba.h declares (again a header and a version of its own)
 BA_SYMBOLS = ["msf_ba_version", "msf_bundle_adjust", "msf_bundle_adjust_device"]
+
+# every symbol include/msf_global_ba.h declares (again a header and a version of its own)
+GLOBAL_BA_SYMBOLS = ["msf_global_ba_version", "msf_global_ba_tile_rows", "msf_global_bundle_adjust",
+                     "msf_global_bundle_adjust_device"]
+GBA_MAX_FREE_CAMS = 1024
 
 
 class Config(C.Structure):
@@ -293,6 +298,11 @@ def load():
     L.msf_bundle_adjust.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, C.POINTER(BaParams), C.POINTER(BaResult)]
     L.msf_bundle_adjust_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, vp,
                                            C.POINTER(BaParams), C.POINTER(BaResult), vp]
+    L.msf_global_ba_version.restype = C.c_int
+    L.msf_global_ba_tile_rows.restype = C.c_int
+    L.msf_global_bundle_adjust.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, C.POINTER(BaParams), C.POINTER(BaResult)]
+    L.msf_global_bundle_adjust_device.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, C.POINTER(BaParams),
+                                                  C.POINTER(BaResult), vp]
     L.msf_render_match_image.argtypes = [vp, C.POINTER(Image), C.POINTER(Image), vp, i32, vp, vp, vp, i64]
     L.msf_weights_info.argtypes = [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(i64)]
     L.msf_convert_weights.argtypes = [C.c_char_p, C.c_char_p]

@@ -2,7 +2,9 @@
 // Optimizer::BundleAdjustment (:71-215) and of the parts of g2o they drive: a Levenberg-Marquardt over SE3 poses and
 // 3-D points joined by EdgeSE3ProjectXYZ edges, the points eliminated by a Schur complement.  Plain C++ shared by
 // ba_kernels.hip and by a host build (tests/cpp/ba_solve_host.cpp), so every stage can be checked against float64
-// numpy without a GPU.  Both builds use -ffp-contract=off; libm: sqrt, fabs, sin, cos.  Every step is in f64; poses,
+// numpy without a GPU.  Both builds use -ffp-contract=off; libm: sqrt, fabs (sin and cos of a pose update are
+// pose::sin_cos, plain multiplies and adds: a device's and a host's libm round some arguments differently, and the host
+// build is what both device paths have to match bit for bit).  Every step is in f64; poses,
 // points, pixels and intrinsics are f32 and are promoted on load.  Estimate, estimate_of, matrix_of, se3_exp, the
 // oplus (moved), the edge error and the Huber kernel are those of pose_solve.h.
 //
@@ -287,38 +289,73 @@ MSF_HD void sym3_mul(const double* m, const double* x, double* y) {
   y[2] = m[2] * x[0] + m[4] * x[1] + m[5] * x[2];
 }
 
+// The bodies of the phases, one index each: the teams of this file and the grid-wide launches of gba_solve.h /
+// gba_kernels.hip call the same code.
+
+// an edge whose indices may not be used: out of range, or its point below the edge before it
+MSF_HD bool edge_malformed(const Problem& p, int e) {
+  const int c = p.edge_cam[e], q = p.edge_point[e];
+  return c < 0 || c >= p.n_cams || q < 0 || q >= p.n_points || (e > 0 && p.edge_point[e - 1] > q);
+}
+
+// the free cameras in camera order (one thread) -> their count
+MSF_HD int map_free_cameras(const Problem& p, const Scratch& w) {
+  int nf = 0;
+  for (int c = 0; c < p.n_cams; c++) {
+    const bool fixed = p.cam_fixed[c] != 0;
+    w.free_of[c] = fixed ? -1 : nf;
+    if (!fixed) w.free_cam[nf++] = c;
+  }
+  return nf;
+}
+
+// camera c: how many edges it has (into cam_active) and its entry estimate
+MSF_HD void count_camera_edges(const Problem& p, const Scratch& w, int c) {
+  int k = 0;
+  for (int e = 0; e < p.n_edges; e++) k += p.edge_cam[e] == c;
+  w.cam_active[c] = k;
+  w.cam[c] = pose::estimate_of(p.cam_tcw + 12 * (long long)c);
+}
+
+// camera c collects its edges in edge order from cam_start[c] on
+MSF_HD void collect_camera_edges(const Problem& p, const Scratch& w, int c) {
+  int at = w.cam_start[c];
+  for (int e = 0; e < p.n_edges; e++)
+    if (p.edge_cam[e] == c) w.cam_edges[at++] = e;
+}
+
+// point q: its edges [pt_start[q], pt_end[q]) by two lower bounds in the sorted edge_point, and its entry estimate
+MSF_HD void prepare_point(const Problem& p, const Scratch& w, int q) {
+  for (int side = 0; side < 2; side++) {
+    int lo = 0, hi = p.n_edges;
+    while (lo < hi) {
+      const int mid = lo + (hi - lo) / 2;
+      if (p.edge_point[mid] < q + side) lo = mid + 1;
+      else hi = mid;
+    }
+    (side ? w.pt_end : w.pt_start)[q] = lo;
+  }
+  for (int k = 0; k < 3; k++) w.pt[3 * (long long)q + k] = (double)p.points[3 * (long long)q + k];
+}
+
 // Checks every index before use and builds what does not change: the free-camera map, both CSRs and the estimates.
 // false: malformed (nothing but the scratch was written).  *n_free: the free cameras.
 template <class Team>
 MSF_HD bool prepare(const Team& team, const Problem& p, const Scratch& w, int* n_free) {
   bool bad = false;
   team.each(p.n_edges, [&](int e) {
-    const int c = p.edge_cam[e], q = p.edge_point[e];
-    if (c < 0 || c >= p.n_cams || q < 0 || q >= p.n_points || (e > 0 && p.edge_point[e - 1] > q)) bad = true;
+    if (edge_malformed(p, e)) bad = true;
   });
   if (team.any(bad)) return false;
   // the free cameras in camera order; the count travels through the problem's word
-  if (team.leader()) {
-    int nf = 0;
-    for (int c = 0; c < p.n_cams; c++) {
-      const bool fixed = p.cam_fixed[c] != 0;
-      w.free_of[c] = fixed ? -1 : nf;
-      if (!fixed) w.free_cam[nf++] = c;
-    }
-    *w.word = nf;
-  }
+  if (team.leader()) *w.word = map_free_cameras(p, w);
   team.join();
   const int nf = *w.word;
   team.join();
   *n_free = nf;
   if (nf > w.max_free) return false;
   // the camera-side CSR: counts, the leader's prefix sum, then every camera collects its edges in edge order
-  team.each(p.n_cams, [&](int c) {
-    int k = 0;
-    for (int e = 0; e < p.n_edges; e++) k += p.edge_cam[e] == c;
-    w.cam_active[c] = k;
-    w.cam[c] = pose::estimate_of(p.cam_tcw + 12 * (long long)c);
-  });
+  team.each(p.n_cams, [&](int c) { count_camera_edges(p, w, c); });
   if (team.leader()) {
     int at = 0;
     for (int c = 0; c < p.n_cams; c++) {
@@ -328,40 +365,68 @@ MSF_HD bool prepare(const Team& team, const Problem& p, const Scratch& w, int* n
     }
   }
   team.join();
-  team.each(p.n_cams, [&](int c) {
-    int at = w.cam_start[c];
-    for (int e = 0; e < p.n_edges; e++)
-      if (p.edge_cam[e] == c) w.cam_edges[at++] = e;
-  });
-  // a point's edges: [pt_start[q], pt_end[q]) by two lower bounds in the sorted edge_point
-  team.each(p.n_points, [&](int q) {
-    for (int side = 0; side < 2; side++) {
-      int lo = 0, hi = p.n_edges;
-      while (lo < hi) {
-        const int mid = lo + (hi - lo) / 2;
-        if (p.edge_point[mid] < q + side) lo = mid + 1;
-        else hi = mid;
-      }
-      (side ? w.pt_end : w.pt_start)[q] = lo;
-    }
-    for (int k = 0; k < 3; k++) w.pt[3 * (long long)q + k] = (double)p.points[3 * (long long)q + k];
-  });
+  team.each(p.n_cams, [&](int c) { collect_camera_edges(p, w, c); });
+  team.each(p.n_points, [&](int q) { prepare_point(p, w, q); });
   return true;
+}
+
+MSF_HD void count_active_camera(const Scratch& w, int c) {
+  int k = 0;
+  for (int at = w.cam_start[c]; at < w.cam_end[c]; at++) k += w.active[w.cam_edges[at]];
+  w.cam_active[c] = k;
+}
+
+MSF_HD void count_active_point(const Scratch& w, int q) {
+  int k = 0;
+  for (int e = w.pt_start[q]; e < w.pt_end[q]; e++) k += w.active[e];
+  w.pt_active[q] = k;
 }
 
 // how many active edges every camera and point has in the round
 template <class Team>
 MSF_HD void count_active(const Team& team, const Problem& p, const Scratch& w) {
-  team.each(p.n_cams, [&](int c) {
-    int k = 0;
-    for (int at = w.cam_start[c]; at < w.cam_end[c]; at++) k += w.active[w.cam_edges[at]];
-    w.cam_active[c] = k;
-  });
-  team.each(p.n_points, [&](int q) {
-    int k = 0;
-    for (int e = w.pt_start[q]; e < w.pt_end[q]; e++) k += w.active[e];
-    w.pt_active[q] = k;
-  });
+  team.each(p.n_cams, [&](int c) { count_active_camera(w, c); });
+  team.each(p.n_points, [&](int q) { count_active_point(w, q); });
+}
+
+// Hpp, b_p, cost (redp) and largest |diagonal| (redq) of point q over its active edges, in edge order
+MSF_HD void point_system(const Scratch& w, int q) {
+  double h[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0}, cost = 0.0;
+  for (int e = w.pt_start[q]; e < w.pt_end[q]; e++) {
+    if (!w.active[e]) continue;
+    const double* l = w.lin + (long long)e * kLin;
+    int at = 0;
+    for (int r = 0; r < 3; r++)
+      for (int c = r; c < 3; c++) h[at++] += l[20] * (l[12 + r] * l[12 + c] + l[15 + r] * l[15 + c]);
+    for (int r = 0; r < 3; r++) b[r] += -(l[20] * (l[12 + r] * l[18] + l[15 + r] * l[19]));
+    cost += l[21];
+  }
+  for (int k = 0; k < 6; k++) w.Hpp[6 * (long long)q + k] = h[k];
+  for (int k = 0; k < 3; k++) w.bp[3 * (long long)q + k] = b[k];
+  w.redp[q] = cost;
+  double top = fabs(h[0]);
+  top = fabs(h[3]) > top ? fabs(h[3]) : top;
+  w.redq[q] = fabs(h[5]) > top ? fabs(h[5]) : top;
+}
+
+// entry i = (free camera, one of the 21 of Hcc's upper triangle or the 6 of b_c) over the camera's CSR, in its order
+MSF_HD void camera_system(const Scratch& w, int i) {
+  const int f = i / 27, k = i % 27, c = w.free_cam[f];
+  int r = 0, cc = k - 21;
+  if (k < 21) {
+    int left = k;
+    while (left >= 6 - r) left -= 6 - r, r++;
+    cc = r + left;
+  }
+  double sum = 0.0;
+  for (int at = w.cam_start[c]; at < w.cam_end[c]; at++) {
+    const int e = w.cam_edges[at];
+    if (!w.active[e]) continue;
+    const double* l = w.lin + (long long)e * kLin;
+    if (k < 21) sum += l[20] * (l[r] * l[cc] + l[6 + r] * l[6 + cc]);
+    else sum += -(l[20] * (l[cc] * l[18] + l[6 + cc] * l[19]));
+  }
+  w.Hcc[i] = sum;
 }
 
 // H and b of the active edges at the estimates; -> the cost.  redq is left holding every point's largest |diagonal|.
@@ -370,84 +435,58 @@ MSF_HD double build_system(const Team& team, const Problem& p, const Params& prm
   team.each(p.n_edges, [&](int e) {
     if (w.active[e]) linearize(p, prm, huber, w, e);
   });
-  team.each(p.n_points, [&](int q) {
-    double h[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0}, cost = 0.0;
-    for (int e = w.pt_start[q]; e < w.pt_end[q]; e++) {
-      if (!w.active[e]) continue;
-      const double* l = w.lin + (long long)e * kLin;
-      int at = 0;
-      for (int r = 0; r < 3; r++)
-        for (int c = r; c < 3; c++) h[at++] += l[20] * (l[12 + r] * l[12 + c] + l[15 + r] * l[15 + c]);
-      for (int r = 0; r < 3; r++) b[r] += -(l[20] * (l[12 + r] * l[18] + l[15 + r] * l[19]));
-      cost += l[21];
-    }
-    for (int k = 0; k < 6; k++) w.Hpp[6 * (long long)q + k] = h[k];
-    for (int k = 0; k < 3; k++) w.bp[3 * (long long)q + k] = b[k];
-    w.redp[q] = cost;
-    double top = fabs(h[0]);
-    top = fabs(h[3]) > top ? fabs(h[3]) : top;
-    w.redq[q] = fabs(h[5]) > top ? fabs(h[5]) : top;
-  });
-  team.each(nf * 27, [&](int i) {
-    const int f = i / 27, k = i % 27, c = w.free_cam[f];
-    int r = 0, cc = k - 21;
-    if (k < 21) {
-      int left = k;
-      while (left >= 6 - r) left -= 6 - r, r++;
-      cc = r + left;
-    }
-    double sum = 0.0;
-    for (int at = w.cam_start[c]; at < w.cam_end[c]; at++) {
-      const int e = w.cam_edges[at];
-      if (!w.active[e]) continue;
-      const double* l = w.lin + (long long)e * kLin;
-      if (k < 21) sum += l[20] * (l[r] * l[cc] + l[6 + r] * l[6 + cc]);
-      else sum += -(l[20] * (l[cc] * l[18] + l[6 + cc] * l[19]));
-    }
-    w.Hcc[i] = sum;
-  });
+  team.each(p.n_points, [&](int q) { point_system(w, q); });
+  team.each(nf * 27, [&](int i) { camera_system(w, i); });
   return tree<false>(team, w.redp, p.n_points);
 }
 
-// S (lower triangle, column-major, ld = n + 1) and b_S (row n) at lambda; every row by its owner
-template <class Team>
-MSF_HD void build_schur(const Team& team, const Problem& p, const Scratch& w, int nf, double lambda) {
+// what column c of the 6 x 3 block W2 takes from an entry of S, y being Hpp^-1 times the row's own row of W
+MSF_HD double schur_term(const double* y, const double* W2, int c) {
+  return y[0] * W2[3 * c] + y[1] * W2[3 * c + 1] + y[2] * W2[3 * c + 2];
+}
+
+// row `row` of S (lower triangle, column-major, ld = n + 1) and its entry of b_S (row n) at lambda
+MSF_HD void schur_row(const Problem& p, const Scratch& w, int nf, double lambda, int row) {
   const int n = 6 * nf;
   const long long ld = n + 1;
-  team.each(n, [&](int row) {
-    const int fi = row / 6, r = row % 6, ci = w.free_cam[fi];
-    const double* H = w.Hcc + 27 * (long long)fi;
-    const bool moves = w.cam_active[ci] > 0;
-    for (int col = 0; col <= row; col++) {
-      double v = 0.0;
-      if (col / 6 == fi) {
-        const int c = col % 6;
-        v = moves ? H[tri(c, r)] + (c == r ? lambda : 0.0) : (c == r ? 1.0 : 0.0);
-      }
-      w.S[col * ld + row] = v;
+  const int fi = row / 6, r = row % 6, ci = w.free_cam[fi];
+  const double* H = w.Hcc + 27 * (long long)fi;
+  const bool moves = w.cam_active[ci] > 0;
+  for (int col = 0; col <= row; col++) {
+    double v = 0.0;
+    if (col / 6 == fi) {
+      const int c = col % 6;
+      v = moves ? H[tri(c, r)] + (c == r ? lambda : 0.0) : (c == r ? 1.0 : 0.0);
     }
-    double bs = moves ? H[21 + r] : 0.0;
-    for (int at = w.cam_start[ci]; at < w.cam_end[ci]; at++) {
-      const int e = w.cam_edges[at];
-      if (!w.active[e]) continue;
-      const int q = p.edge_point[e];
-      const double* We = w.W + 18 * (long long)e + 3 * r;
-      double y[3];
-      sym3_mul(w.inv + 6 * (long long)q, We, y);
-      const double* b = w.bp + 3 * (long long)q;
-      bs -= y[0] * b[0] + y[1] * b[1] + y[2] * b[2];
-      for (int e2 = w.pt_start[q]; e2 < w.pt_end[q]; e2++) {
-        if (!w.active[e2]) continue;
-        const int fj = w.free_of[p.edge_cam[e2]];
-        if (fj < 0 || fj > fi) continue;
-        const double* W2 = w.W + 18 * (long long)e2;
-        const int last = fj == fi ? r : 5;
-        for (int c = 0; c <= last; c++)
-          w.S[(6 * fj + c) * ld + row] -= y[0] * W2[3 * c] + y[1] * W2[3 * c + 1] + y[2] * W2[3 * c + 2];
-      }
+    w.S[col * ld + row] = v;
+  }
+  double bs = moves ? H[21 + r] : 0.0;
+  for (int at = w.cam_start[ci]; at < w.cam_end[ci]; at++) {
+    const int e = w.cam_edges[at];
+    if (!w.active[e]) continue;
+    const int q = p.edge_point[e];
+    const double* We = w.W + 18 * (long long)e + 3 * r;
+    double y[3];
+    sym3_mul(w.inv + 6 * (long long)q, We, y);
+    const double* b = w.bp + 3 * (long long)q;
+    bs -= y[0] * b[0] + y[1] * b[1] + y[2] * b[2];
+    for (int e2 = w.pt_start[q]; e2 < w.pt_end[q]; e2++) {
+      if (!w.active[e2]) continue;
+      const int fj = w.free_of[p.edge_cam[e2]];
+      if (fj < 0 || fj > fi) continue;
+      const double* W2 = w.W + 18 * (long long)e2;
+      const int last = fj == fi ? r : 5;
+      for (int c = 0; c <= last; c++)
+        w.S[(6 * fj + c) * ld + row] -= schur_term(y, W2, c);
     }
-    w.S[row * ld + n] = bs;
-  });
+  }
+  w.S[row * ld + n] = bs;
+}
+
+// S and b_S at lambda; every row by its owner
+template <class Team>
+MSF_HD void build_schur(const Team& team, const Problem& p, const Scratch& w, int nf, double lambda) {
+  team.each(6 * nf, [&](int row) { schur_row(p, w, nf, lambda, row); });
 }
 
 // L L' = S in place, left-looking, with b_S as row n, so that row n ends as y = L^-1 b_S; the diagonal of L goes to
@@ -486,15 +525,112 @@ MSF_HD void back_substitute(const Team& team, double* S, int n, const double* di
     });
 }
 
+MSF_HD void write_camera(const Scratch& w, double* cam_out, int c) {
+  for (int k = 0; k < 4; k++) cam_out[7 * (long long)c + k] = w.cam[c].q[k];
+  for (int k = 0; k < 3; k++) cam_out[7 * (long long)c + 4 + k] = w.cam[c].t[k];
+}
+
 template <class Team>
 MSF_HD void write_estimates(const Team& team, const Problem& p, const Scratch& w, double* cam_out, double* pt_out) {
   if (cam_out)
-    team.each(p.n_cams, [&](int c) {
-      for (int k = 0; k < 4; k++) cam_out[7 * (long long)c + k] = w.cam[c].q[k];
-      for (int k = 0; k < 3; k++) cam_out[7 * (long long)c + 4 + k] = w.cam[c].t[k];
-    });
+    team.each(p.n_cams, [&](int c) { write_camera(w, cam_out, c); });
   if (pt_out)
     team.each(p.n_points * 3, [&](int k) { pt_out[k] = w.pt[k]; });
+}
+
+// it_Hcc / it_bc of camera c in `slot`: 0 for a fixed camera
+MSF_HD void write_camera_system(const Problem& p, const Scratch& w, const Out& o, int slot, int c) {
+  const long long nc = p.n_cams;
+  const int f = w.free_of[c];
+  for (int k = 0; k < 21; k++)
+    if (o.it_Hcc) o.it_Hcc[(slot * nc + c) * 21 + k] = f < 0 ? 0.0 : w.Hcc[27 * (long long)f + k];
+  for (int k = 0; k < 6; k++)
+    if (o.it_bc) o.it_bc[(slot * nc + c) * 6 + k] = f < 0 ? 0.0 : w.Hcc[27 * (long long)f + 21 + k];
+}
+
+// the largest |diagonal| of free camera f's block, into redc
+MSF_HD void camera_top(const Scratch& w, int f) {
+  double top = 0.0;
+  for (int r = 0; r < 6; r++) {
+    const double d = fabs(w.Hcc[27 * (long long)f + tri(r, r)]);
+    top = d > top ? d : top;
+  }
+  w.redc[f] = top;
+}
+
+// (Hpp + lambda I)^-1 of point q, 0 for a point without an active edge; false: the block failed
+MSF_HD bool invert_point(const Scratch& w, double lam, int q) {
+  double* inv = w.inv + 6 * (long long)q;
+  if (!w.pt_active[q]) {
+    for (int k = 0; k < 6; k++) inv[k] = 0.0;
+    return true;
+  }
+  return invert3(w.Hpp + 6 * (long long)q, lam, inv);
+}
+
+// dx_p, the trial point and the point's part of the gain's denominator (redq)
+MSF_HD void point_step(const Problem& p, const Scratch& w, double lam, int q) {
+  const double* b = w.bp + 3 * (long long)q;
+  double t[3] = {b[0], b[1], b[2]}, dx[3];
+  for (int e = w.pt_start[q]; e < w.pt_end[q]; e++) {
+    if (!w.active[e]) continue;
+    const int f = w.free_of[p.edge_cam[e]];
+    if (f < 0) continue;
+    const double* We = w.W + 18 * (long long)e;
+    const double* xc = w.x + 6 * f;
+    for (int k = 0; k < 3; k++)
+      for (int r = 0; r < 6; r++) t[k] -= We[3 * r + k] * xc[r];
+  }
+  sym3_mul(w.inv + 6 * (long long)q, t, dx);
+  double scale = 0.0;
+  for (int k = 0; k < 3; k++) {
+    w.dxp[3 * (long long)q + k] = dx[k];
+    w.pt_trial[3 * (long long)q + k] = w.pt_active[q] ? w.pt[3 * (long long)q + k] + dx[k] : w.pt[3 * (long long)q + k];
+    scale += dx[k] * (lam * dx[k] + b[k]);
+  }
+  w.redq[q] = scale;
+}
+
+// the trial estimate of camera c and, for a free one, its part of the gain's denominator (redc)
+MSF_HD void camera_step(const Scratch& w, double lam, int c) {
+  const int f = w.free_of[c];
+  w.cam_trial[c] = w.cam[c];
+  if (f < 0) return;
+  double scale = 0.0;
+  if (w.cam_active[c] > 0) {
+    const double* dx = w.x + 6 * f;
+    w.cam_trial[c] = pose::moved<true>(w.cam[c], dx);
+    for (int k = 0; k < 6; k++) scale += dx[k] * (lam * dx[k] + w.Hcc[27 * (long long)f + 21 + k]);
+  }
+  w.redc[f] = scale;
+}
+
+// the cost of point q's active edges at the trial estimates, in edge order, into redp
+MSF_HD void point_trial_cost(const Problem& p, const Params& prm, bool huber, const Scratch& w, int q) {
+  double c = 0.0;
+  for (int e = w.pt_start[q]; e < w.pt_end[q]; e++)
+    if (w.active[e]) c += edge_cost(p, prm, huber, w.cam_trial, w.pt_trial, e);
+  w.redp[q] = c;
+}
+
+// a trial's verdict from its figures: the expressions of OptimizationAlgorithmLevenberg
+MSF_HD double gain_of(double cost, double trial_cost, double scale_c, double scale_p) {
+  return (cost - trial_cost) / ((1e-3 + scale_c) + scale_p);
+}
+
+// lambda and ni after a trial; -> the run of trials ends without an accepted one
+MSF_HD bool next_lambda(bool accepted, double gain, double* lambda, double* ni) {
+  if (accepted) {
+    const double y = 2 * gain - 1;
+    double alpha = 1.0 - y * y * y;
+    alpha = alpha < 2.0 / 3.0 ? alpha : 2.0 / 3.0;
+    *lambda *= alpha > 1.0 / 3.0 ? alpha : 1.0 / 3.0;
+    *ni = 2.0;
+    return false;
+  }
+  *lambda *= *ni;
+  *ni *= 2.0;
+  return !finite(*lambda) || gain == 0;
 }
 
 // One iteration of OptimizationAlgorithmLevenberg::solve over BlockSolver_6_3: the system once at the entry estimate,
@@ -509,24 +645,11 @@ MSF_HD int iteration(const Team& team, const Problem& p, const Params& prm, cons
                   o.it_point_in ? o.it_point_in + slot * np * 3 : nullptr);
   const double cost = build_system(team, p, prm, huber, w, nf);
   if (o.it_Hcc || o.it_bc)
-    team.each(p.n_cams, [&](int c) {
-      const int f = w.free_of[c];
-      for (int k = 0; k < 21; k++)
-        if (o.it_Hcc) o.it_Hcc[(slot * nc + c) * 21 + k] = f < 0 ? 0.0 : w.Hcc[27 * (long long)f + k];
-      for (int k = 0; k < 6; k++)
-        if (o.it_bc) o.it_bc[(slot * nc + c) * 6 + k] = f < 0 ? 0.0 : w.Hcc[27 * (long long)f + 21 + k];
-    });
+    team.each(p.n_cams, [&](int c) { write_camera_system(p, w, o, slot, c); });
   if (o.it_Hpp) team.each(p.n_points * 6, [&](int k) { o.it_Hpp[slot * np * 6 + k] = w.Hpp[k]; });
   if (o.it_bp) team.each(p.n_points * 3, [&](int k) { o.it_bp[slot * np * 3 + k] = w.bp[k]; });
   if (first) {
-    team.each(nf, [&](int f) {
-      double top = 0.0;
-      for (int r = 0; r < 6; r++) {
-        const double d = fabs(w.Hcc[27 * (long long)f + tri(r, r)]);
-        top = d > top ? d : top;
-      }
-      w.redc[f] = top;
-    });
+    team.each(nf, [&](int f) { camera_top(w, f); });
     const double top_p = tree<true>(team, w.redq, p.n_points), top_c = tree<true>(team, w.redc, nf);
     *lambda = 1e-5 * (top_c > top_p ? top_c : top_p);
     *ni = 2.0;
@@ -541,12 +664,7 @@ MSF_HD int iteration(const Team& team, const Problem& p, const Params& prm, cons
     double gain = -1.0, trial_cost = kDblMax;
     bool bad = false;
     team.each(p.n_points, [&](int q) {
-      double* inv = w.inv + 6 * (long long)q;
-      if (!w.pt_active[q]) {
-        for (int k = 0; k < 6; k++) inv[k] = 0.0;
-        return;
-      }
-      if (!invert3(w.Hpp + 6 * (long long)q, lam, inv)) bad = true;
+      if (!invert_point(w, lam, q)) bad = true;
     });
     bool solved = !team.any(bad) && finite(lam);
     if (solved) {
@@ -555,64 +673,21 @@ MSF_HD int iteration(const Team& team, const Problem& p, const Params& prm, cons
     }
     if (solved) {
       back_substitute(team, w.S, n, w.diag, w.x);
-      // dx_p, the trial point and the point's part of the gain's denominator
-      team.each(p.n_points, [&](int q) {
-        const double* b = w.bp + 3 * (long long)q;
-        double t[3] = {b[0], b[1], b[2]}, dx[3];
-        for (int e = w.pt_start[q]; e < w.pt_end[q]; e++) {
-          if (!w.active[e]) continue;
-          const int f = w.free_of[p.edge_cam[e]];
-          if (f < 0) continue;
-          const double* We = w.W + 18 * (long long)e;
-          const double* xc = w.x + 6 * f;
-          for (int k = 0; k < 3; k++)
-            for (int r = 0; r < 6; r++) t[k] -= We[3 * r + k] * xc[r];
-        }
-        sym3_mul(w.inv + 6 * (long long)q, t, dx);
-        double scale = 0.0;
-        for (int k = 0; k < 3; k++) {
-          w.dxp[3 * (long long)q + k] = dx[k];
-          w.pt_trial[3 * (long long)q + k] = w.pt_active[q] ? w.pt[3 * (long long)q + k] + dx[k] : w.pt[3 * (long long)q + k];
-          scale += dx[k] * (lam * dx[k] + b[k]);
-        }
-        w.redq[q] = scale;
-      });
-      team.each(p.n_cams, [&](int c) {
-        const int f = w.free_of[c];
-        w.cam_trial[c] = w.cam[c];
-        if (f < 0) return;
-        double scale = 0.0;
-        if (w.cam_active[c] > 0) {
-          const double* dx = w.x + 6 * f;
-          w.cam_trial[c] = pose::moved(w.cam[c], dx);
-          for (int k = 0; k < 6; k++) scale += dx[k] * (lam * dx[k] + w.Hcc[27 * (long long)f + 21 + k]);
-        }
-        w.redc[f] = scale;
-      });
-      team.each(p.n_points, [&](int q) {
-        double c = 0.0;
-        for (int e = w.pt_start[q]; e < w.pt_end[q]; e++)
-          if (w.active[e]) c += edge_cost(p, prm, huber, w.cam_trial, w.pt_trial, e);
-        w.redp[q] = c;
-      });
+      team.each(p.n_points, [&](int q) { point_step(p, w, lam, q); });
+      team.each(p.n_cams, [&](int c) { camera_step(w, lam, c); });
+      team.each(p.n_points, [&](int q) { point_trial_cost(p, prm, huber, w, q); });
       trial_cost = tree<false>(team, w.redp, p.n_points);
       const double scale_c = tree<false>(team, w.redc, nf), scale_p = tree<false>(team, w.redq, p.n_points);
-      gain = (cost - trial_cost) / ((1e-3 + scale_c) + scale_p);
+      gain = gain_of(cost, trial_cost, scale_c, scale_p);
     }
     if (solved && gain > 0 && finite(trial_cost)) {
-      const double y = 2 * gain - 1;
-      double alpha = 1.0 - y * y * y;
-      alpha = alpha < 2.0 / 3.0 ? alpha : 2.0 / 3.0;
-      *lambda *= alpha > 1.0 / 3.0 ? alpha : 1.0 / 3.0;
-      *ni = 2.0;
+      next_lambda(true, gain, lambda, ni);
       team.each(p.n_cams, [&](int c) { w.cam[c] = w.cam_trial[c]; });
       team.each(p.n_points * 3, [&](int k) { w.pt[k] = w.pt_trial[k]; });
       cost_out = trial_cost;
       accepted = true;
-    } else {
-      *lambda *= *ni;
-      *ni *= 2.0;
-      if (!finite(*lambda) || gain == 0) break;
+    } else if (next_lambda(false, gain, lambda, ni)) {
+      break;
     }
   }
   write_estimates(team, p, w, o.it_cam_out ? o.it_cam_out + slot * nc * 7 : nullptr,
@@ -625,6 +700,47 @@ MSF_HD int iteration(const Team& team, const Problem& p, const Params& prm, cons
     if (o.it_cost_out) o.it_cost_out[slot] = cost_out;
   }
   return accepted ? trials : -trials;
+}
+
+// :507-518: the edges round 1 keeps, and every edge's chi2 at the estimate round 0 kept
+MSF_HD void reclassify_edge(const Problem& p, const Params& prm, const Scratch& w, int e) {
+  const bool f = flagged_at(p, prm, w.cam, w.pt, e, &w.chi2_0[e]);
+  w.active[e] = f ? 0 : 1;
+}
+
+MSF_HD void write_round0_flag(const Problem& p, const Params& prm, const Scratch& w, const Out& o, int e) {
+  double chi2;
+  o.round_flags[2 * (long long)e] = flagged_at(p, prm, w.cam, w.pt, e, &chi2) ? 1 : 0;
+}
+
+// :530-540
+MSF_HD void write_final_flag(const Problem& p, const Params& prm, const Scratch& w, const Out& o, int rounds_run, int e) {
+  double chi2;
+  bool f = flagged_at(p, prm, w.cam, w.pt, e, &chi2);
+  if (rounds_run == 2 && !w.active[e]) {
+    double rt[12], xc[3], err[2];
+    edge_at(p, prm.cam, w.cam, w.pt, e, rt, xc, err);
+    f = w.chi2_0[e] > prm.chi2 || !(xc[2] > 0);
+  }
+  if (o.outliers) o.outliers[e] = f ? 1 : 0;
+  if (o.round_flags && rounds_run == 2) o.round_flags[2 * (long long)e + 1] = f ? 1 : 0;
+}
+
+MSF_HD void write_final_camera(const Problem& p, const Scratch& w, const Out& o, int rounds_run, int c) {
+  double rt[12];
+  pose::matrix_of(w.cam[c], rt);
+  const bool as_came = w.free_of[c] < 0 || rounds_run == 0;
+  for (int k = 0; k < 12; k++) {
+    const float in = p.cam_tcw[12 * (long long)c + k];
+    const double v = as_came ? (double)in : rt[k];
+    if (o.cam_pose_f64) o.cam_pose_f64[12 * (long long)c + k] = v;
+    if (o.cam_tcw) o.cam_tcw[12 * (long long)c + k] = as_came ? in : (float)v;
+  }
+}
+
+MSF_HD void write_final_point(const Scratch& w, const Out& o, int k) {
+  if (o.points_f64) o.points_f64[k] = w.pt[k];
+  if (o.points) o.points[k] = (float)w.pt[k];
 }
 
 // the stop word, read by the leader alone and agreed on by the team
@@ -652,10 +768,7 @@ MSF_HD int bundle_adjust(const Team& team, const Problem& p, const Params& prm, 
   for (int round = 0; round < prm.n_rounds && !stopped; round++) {
     if (stop_set(team, stop)) break;
     if (round == 1) {   // :507-518
-      team.each(p.n_edges, [&](int e) {
-        const bool f = flagged_at(p, prm, w.cam, w.pt, e, &w.chi2_0[e]);
-        w.active[e] = f ? 0 : 1;
-      });
+      team.each(p.n_edges, [&](int e) { reclassify_edge(p, prm, w, e); });
     }
     count_active(team, p, w);
     double lambda = 0.0, ni = 2.0;
@@ -672,39 +785,13 @@ MSF_HD int bundle_adjust(const Team& team, const Problem& p, const Params& prm, 
     rounds_run = round + 1;
     if (team.leader() && o.round_iterations) o.round_iterations[round] = it;
     if (o.round_flags && round == 0)
-      team.each(p.n_edges, [&](int e) {
-        double chi2;
-        o.round_flags[2 * (long long)e] = flagged_at(p, prm, w.cam, w.pt, e, &chi2) ? 1 : 0;
-      });
+      team.each(p.n_edges, [&](int e) { write_round0_flag(p, prm, w, o, e); });
   }
   // :530-540
   if (o.outliers || o.round_flags)
-    team.each(p.n_edges, [&](int e) {
-      double chi2;
-      bool f = flagged_at(p, prm, w.cam, w.pt, e, &chi2);
-      if (rounds_run == 2 && !w.active[e]) {
-        double rt[12], xc[3], err[2];
-        edge_at(p, prm.cam, w.cam, w.pt, e, rt, xc, err);
-        f = w.chi2_0[e] > prm.chi2 || !(xc[2] > 0);
-      }
-      if (o.outliers) o.outliers[e] = f ? 1 : 0;
-      if (o.round_flags && rounds_run == 2) o.round_flags[2 * (long long)e + 1] = f ? 1 : 0;
-    });
-  team.each(p.n_cams, [&](int c) {
-    double rt[12];
-    pose::matrix_of(w.cam[c], rt);
-    const bool as_came = w.free_of[c] < 0 || rounds_run == 0;
-    for (int k = 0; k < 12; k++) {
-      const float in = p.cam_tcw[12 * (long long)c + k];
-      const double v = as_came ? (double)in : rt[k];
-      if (o.cam_pose_f64) o.cam_pose_f64[12 * (long long)c + k] = v;
-      if (o.cam_tcw) o.cam_tcw[12 * (long long)c + k] = as_came ? in : (float)v;
-    }
-  });
-  team.each(p.n_points * 3, [&](int k) {
-    if (o.points_f64) o.points_f64[k] = w.pt[k];
-    if (o.points) o.points[k] = (float)w.pt[k];
-  });
+    team.each(p.n_edges, [&](int e) { write_final_flag(p, prm, w, o, rounds_run, e); });
+  team.each(p.n_cams, [&](int c) { write_final_camera(p, w, o, rounds_run, c); });
+  team.each(p.n_points * 3, [&](int k) { write_final_point(w, o, k); });
   return rounds_run;
 }
 

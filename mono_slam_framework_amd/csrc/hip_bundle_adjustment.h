@@ -26,8 +26,12 @@
 //   // BundleAdjustment after a loop (:190-214, nLoopKF != 0): the estimates go to pKF->mTcwGBA / pMP->mPosGBA and
 //   //           mnBAGlobalForKF instead of SetPose / SetWorldPos.
 //
-// More than MSF_BA_MAX_FREE_CAMS free cameras is a failed call (a global bundle adjustment of a larger map stays with
-// g2o).  Header-only and OpenCV-free, like hip_optimizer.h.  See INTEGRATION.md.
+// LocalBundleAdjustment and BundleAdjustment run the problem in one workgroup: more than MSF_BA_MAX_FREE_CAMS free
+// cameras is a failed call.  GlobalBundleAdjustment is Optimizer::GlobalBundleAdjustemnt (:62-69) as
+// LoopClosing::RunGlobalBundleAdjustment calls it over the whole map: the same Problem through
+// msf_global_bundle_adjust_device (include/msf_global_ba.h), up to MSF_GBA_MAX_FREE_CAMS free cameras, spread over
+// the device; where both take a problem they give the same bits.  Header-only and OpenCV-free, like hip_optimizer.h.
+// See INTEGRATION.md.
 #pragma once
 
 #include <cstdint>
@@ -37,6 +41,7 @@
 #include "hip_device_block.h"
 #include "hip_mirror_types.h"
 #include "msf_ba.h"
+#include "msf_global_ba.h"
 
 namespace msf {
 
@@ -84,6 +89,18 @@ class BundleAdjuster {
     return Run(problem, prm, stop);
   }
 
+  // :62-69: BundleAdjustment over the whole map -- every key frame and map point of the caller's Map, key frame 0
+  // fixed -- with up to MSF_GBA_MAX_FREE_CAMS free cameras.  The reference's call is (10, false) with
+  // pbStopFlag = &mbStopGBA.  stop: the device reads a copy taken as the call starts.  Returns when the problem is
+  // finished.  false as for the other two, with MSF_GBA_MAX_FREE_CAMS as the capacity.
+  bool GlobalBundleAdjustment(Problem& problem, int nIterations = 10, bool bRobust = false, const int32_t* stop = nullptr) {
+    msf_ba_params prm = Params();
+    prm.n_rounds = 1;
+    prm.iterations[0] = nIterations;
+    prm.robust[0] = bRobust ? 1 : 0;
+    return Run(problem, prm, stop, true);
+  }
+
  private:
   msf_ba_params Params() const {
     msf_ba_params prm = sized<msf_ba_params>();
@@ -105,7 +122,7 @@ class BundleAdjuster {
     msf_ba_result out;
   };
 
-  bool Run(Problem& pb, const msf_ba_params& prm, const int32_t* stop) {
+  bool Run(Problem& pb, const msf_ba_params& prm, const int32_t* stop, bool whole_map = false) {
     const size_t nc = pb.fixed.size(), np = pb.points.size(), ne = pb.edges.size();
     if (pb.Tcw.size() != nc * 16) return false;
     DeviceBlock mem;
@@ -143,13 +160,18 @@ class BundleAdjuster {
       host.edge_cam[e] = pb.edges[e].camera, host.edge_point[e] = pb.edges[e].point;
       host.edge_obs[2 * e] = pb.edges[e].pixel.x, host.edge_obs[2 * e + 1] = pb.edges[e].pixel.y;
     }
-    if (free_cams > MSF_BA_MAX_FREE_CAMS) return false;
-    if (!mem.upload() ||
-        msf_bundle_adjust_device(handle_, 1, dev.problem, dev.Tcw, dev.fixed, dev.points, dev.edge_cam, dev.edge_point,
-                                 dev.edge_obs, static_cast<int64_t>(nc), static_cast<int64_t>(np), static_cast<int64_t>(ne),
-                                 free_cams > 0 ? free_cams : 1, dev.stop, &prm, &dev.out, nullptr) != MSF_OK ||
-        !mem.download())
-      return false;
+    if (free_cams > (whole_map ? MSF_GBA_MAX_FREE_CAMS : MSF_BA_MAX_FREE_CAMS)) return false;
+    if (!mem.upload()) return false;
+    const int32_t max_free = free_cams > 0 ? free_cams : 1;
+    const int rc = whole_map
+                       ? msf_global_bundle_adjust_device(handle_, desc.n_cams, dev.Tcw, dev.fixed, desc.n_points, dev.points,
+                                                         desc.n_edges, dev.edge_cam, dev.edge_point, dev.edge_obs, max_free,
+                                                         dev.stop, &prm, &dev.out, nullptr)
+                       : msf_bundle_adjust_device(handle_, 1, dev.problem, dev.Tcw, dev.fixed, dev.points, dev.edge_cam,
+                                                  dev.edge_point, dev.edge_obs, static_cast<int64_t>(nc),
+                                                  static_cast<int64_t>(np), static_cast<int64_t>(ne), max_free, dev.stop,
+                                                  &prm, &dev.out, nullptr);
+    if (rc != MSF_OK || !mem.download()) return false;
     if (*host.out.status < 0) return false;   // malformed: an edge index out of range or edges not sorted by point
     pb.rounds_run = *host.out.status;
     for (size_t c = 0; c < nc; c++) std::memcpy(&pb.Tcw[c * 16], host.out.cam_Tcw + c * 12, 48);

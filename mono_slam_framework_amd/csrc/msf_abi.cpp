@@ -15,8 +15,10 @@
 #include "ba_pipeline.h"
 #include "carve.h"
 #include "dev_buf.h"
+#include "gba_pipeline.h"
 #include "loftr_pipeline.h"
 #include "msf_ba.h"
+#include "msf_global_ba.h"
 #include "msf_initializer.h"
 #include "msf_local_mapping.h"
 #include "msf_pnp.h"
@@ -97,6 +99,11 @@ struct msf_handle {
   // msf_bundle_adjust / msf_bundle_adjust_device workspace: the per-problem scratch of ba_solve.h (ba::layout); for the
   // host call also the problem, its descriptor, the stop word and the results
   DevBuf<uint8_t> d_ba;
+  // msf_global_bundle_adjust / msf_global_bundle_adjust_device workspace: gba::layout (the record and the scratch of
+  // one problem, sized by its own free cameras); for the host call also the problem and the results.  The pinned record
+  // is what the host reads after every wait of the Levenberg-Marquardt loop (allocated by the first call).
+  DevBuf<uint8_t> d_gba;
+  msf::gba::Record* h_gba_rec = nullptr;
   std::vector<msf_view> view_stage;   // [2][n]: the query's view once per pair, then the neighbours'
   // msf_render_match_image workspace: the RGB image (allocated once) and the match list + flags (grown on demand)
   DevBuf<uint8_t> d_render;      // [H][2 * W][3]
@@ -615,6 +622,7 @@ void msf_destroy(msf_handle* h) {
   h->orb.destroy();
   h->loftr.destroy();
   if (h->h_pin) hipHostFree(h->h_pin);
+  if (h->h_gba_rec) hipHostFree(h->h_gba_rec);
   const hipStream_t stream = h->stream;
   delete h;   // the device buffers go with their DevBuf members, before the stream
   if (stream) hipStreamDestroy(stream);
@@ -1636,6 +1644,149 @@ int msf_bundle_adjust_device(msf_handle* h, int32_t n_problems, const msf_ba_pro
                           total_points, total_edges, max_free_cams, d_stop};
     HIP_TRY(h, "bundle_adjust", msf::bundle_adjust(n_problems, in, ba_params(params), scratch, to_out(*out), cs.st));
     return cs.finish();
+  });
+}
+
+namespace {
+
+// What msf_global_bundle_adjust keeps in the workspace besides its result arrays and gba::layout: the problem.
+struct GbaPlan {
+  float* cam_tcw = nullptr;
+  uint8_t* cam_fixed = nullptr;
+  float* points = nullptr;
+  int32_t* edge_cam = nullptr;
+  int32_t* edge_point = nullptr;
+  float* edge_obs = nullptr;
+  msf::gba::Scratch scratch{};
+  size_t bytes = 0;
+  uint8_t* base = nullptr;
+};
+
+int gba_pinned(msf_handle* h) {
+  if (!h->h_gba_rec)
+    HIP_TRY(h, "hipHostMalloc(global bundle adjustment record)",
+            hipHostMalloc((void**)&h->h_gba_rec, sizeof(msf::gba::Record), hipHostMallocDefault));
+  return MSF_OK;
+}
+
+}  // namespace
+
+int msf_global_ba_version(void) { return MSF_GLOBAL_BA_VERSION; }
+
+int msf_global_ba_tile_rows(void) { return msf::gba::kTile; }
+
+int msf_global_bundle_adjust(msf_handle* h, int32_t n_cams, const float* cam_Tcw, const uint8_t* cam_fixed,
+                             int32_t n_points, const float* points, int32_t n_edges, const int32_t* edge_cam,
+                             const int32_t* edge_point, const float* edge_obs, const volatile int32_t* stop,
+                             const msf_ba_params* params, msf_ba_result* out) {
+  return guarded(h, "msf_global_bundle_adjust", [&]() -> int {
+    if (const char* fault = ba_fault(params, out))
+      return fail(h, MSF_ERR_INVALID_ARG, std::string("msf_global_bundle_adjust: ") + fault);
+    if (n_cams < 0 || n_points < 0 || n_edges < 0)
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_global_bundle_adjust: a count is negative");
+    if ((n_cams > 0 && (!cam_Tcw || !cam_fixed)) || (n_points > 0 && !points) || (n_edges > 0 && (!edge_cam || !edge_point || !edge_obs)))
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_global_bundle_adjust: a required pointer is NULL (cam_Tcw, cam_fixed, points, edge_cam, edge_point, edge_obs)");
+    for (int32_t e = 0; e < n_edges; e++) {
+      if (edge_cam[e] < 0 || edge_cam[e] >= n_cams || edge_point[e] < 0 || edge_point[e] >= n_points)
+        return fail(h, MSF_ERR_INVALID_ARG, "msf_global_bundle_adjust: an edge index is out of range");
+      if (e > 0 && edge_point[e - 1] > edge_point[e])
+        return fail(h, MSF_ERR_INVALID_ARG, "msf_global_bundle_adjust: the edges are not sorted by point");
+    }
+    int n_free = 0;
+    for (int32_t c = 0; c < n_cams; c++) n_free += cam_fixed[c] == 0;
+    if (n_free > MSF_GBA_MAX_FREE_CAMS)
+      return fail(h, MSF_ERR_CAPACITY, "msf_global_bundle_adjust: more than MSF_GBA_MAX_FREE_CAMS free cameras");
+    CallScope cs{h};
+    if (int rc = cs.enter()) return rc;
+    if (int rc = gba_pinned(h)) return rc;
+    const size_t nc = (size_t)n_cams, np = (size_t)n_points, ne = (size_t)n_edges;
+    size_t units[msf::kBaUnits];
+    msf::ba_units(nc, np, ne, units);
+    msf_ba_result dev{};
+    GbaPlan p;
+    if (int rc = carve(h, h->d_gba, (size_t)1 << 20, "hipMalloc(global bundle adjustment workspace)", [&](msf::Carver& c) {
+          p.base = c.base;
+          p.cam_tcw = c.take<float>(nc * 12);
+          p.cam_fixed = c.take<uint8_t>(nc);
+          p.points = c.take<float>(np * 3);
+          p.edge_cam = c.take<int32_t>(ne);
+          p.edge_point = c.take<int32_t>(ne);
+          p.edge_obs = c.take<float>(ne * 2);
+          msf::carve_result(c, msf::kBaArrays, units, 1, nullptr, *out, &dev);
+          p.bytes = c.off;
+          p.scratch = msf::gba::layout(c, nc, np, ne, n_free);
+        }))
+      return rc;
+    hipStream_t st = cs.st;
+    Drain drain{st};
+    // what the kernels leave alone comes back as 0
+    HIP_TRY(h, "hipMemsetAsync", hipMemsetAsync(p.base, 0, p.bytes, st));
+    if (nc) {
+      HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.cam_tcw, cam_Tcw, nc * 48, hipMemcpyHostToDevice, st));
+      HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.cam_fixed, cam_fixed, nc, hipMemcpyHostToDevice, st));
+    }
+    if (np) HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.points, points, np * 12, hipMemcpyHostToDevice, st));
+    if (ne) {
+      HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.edge_cam, edge_cam, ne * 4, hipMemcpyHostToDevice, st));
+      HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.edge_point, edge_point, ne * 4, hipMemcpyHostToDevice, st));
+      HIP_TRY(h, "hipMemcpyAsync", hipMemcpyAsync(p.edge_obs, edge_obs, ne * 8, hipMemcpyHostToDevice, st));
+    }
+    const msf::GbaCall call{msf::ba::Problem{n_cams, n_points, n_edges, p.cam_tcw, p.cam_fixed, p.points, p.edge_cam,
+                                             p.edge_point, p.edge_obs},
+                            ba_params(params), p.scratch, to_out(dev), nullptr};
+    // the same checking launch as the device entry: the device's verdict is the one that counts
+    HIP_TRY(h, "global_bundle_adjust(check)", msf::gba_check(call, h->h_gba_rec, st));
+    if (h->h_gba_rec->malformed || h->h_gba_rec->n_free != n_free)
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_global_bundle_adjust: the problem changed while the call read it");
+    int status = 0;
+    HIP_TRY(h, "global_bundle_adjust", msf::gba_solve(call, n_free, 0, h->h_gba_rec, stop, st, &status));
+    const msf::Extent all{0, 1, 1, 1, units, units};
+    if (int rc = fetch_result(h, st, msf::kBaArrays, dev, *out, all)) return rc;
+    drain.armed = false;
+    return cs.finish();
+  });
+}
+
+int msf_global_bundle_adjust_device(msf_handle* h, int32_t n_cams, const float* d_cam_Tcw, const uint8_t* d_cam_fixed,
+                                    int32_t n_points, const float* d_points, int32_t n_edges, const int32_t* d_edge_cam,
+                                    const int32_t* d_edge_point, const float* d_edge_obs, int32_t max_free_cams,
+                                    const int32_t* d_stop, const msf_ba_params* params, msf_ba_result* out,
+                                    void* stream) {
+  return guarded(h, "msf_global_bundle_adjust_device", [&]() -> int {
+    if (const char* fault = ba_fault(params, out))
+      return fail(h, MSF_ERR_INVALID_ARG, std::string("msf_global_bundle_adjust_device: ") + fault);
+    if (n_cams < 0 || n_points < 0 || n_edges < 0)
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_global_bundle_adjust_device: a count is negative");
+    if (max_free_cams < 1 || max_free_cams > MSF_GBA_MAX_FREE_CAMS)
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_global_bundle_adjust_device: max_free_cams must be 1..MSF_GBA_MAX_FREE_CAMS");
+    if ((n_cams > 0 && (!d_cam_Tcw || !d_cam_fixed)) || (n_points > 0 && !d_points) ||
+        (n_edges > 0 && (!d_edge_cam || !d_edge_point || !d_edge_obs)))
+      return fail(h, MSF_ERR_INVALID_ARG, "msf_global_bundle_adjust_device: a required pointer is NULL");
+    CallScope cs{h};
+    if (int rc = cs.enter(stream)) return rc;
+    if (int rc = gba_pinned(h)) return rc;
+    const size_t nc = (size_t)n_cams, np = (size_t)n_points, ne = (size_t)n_edges;
+    msf::GbaCall call{msf::ba::Problem{n_cams, n_points, n_edges, d_cam_Tcw, d_cam_fixed, d_points, d_edge_cam,
+                                       d_edge_point, d_edge_obs},
+                      ba_params(params), msf::gba::Scratch{}, to_out(*out), d_stop};
+    // the record alone until the checking launch has passed the indices and counted the free cameras
+    if (int rc = carve(h, h->d_gba, (size_t)1 << 20, "hipMalloc(global bundle adjustment workspace)",
+                       [&](msf::Carver& c) { call.s = msf::gba::layout(c, nc, np, ne, 0); }))
+      return rc;
+    HIP_TRY(h, "global_bundle_adjust(check)", msf::gba_check(call, h->h_gba_rec, cs.st));
+    const int n_free = h->h_gba_rec->n_free;
+    if (h->h_gba_rec->malformed || n_free > max_free_cams) {
+      HIP_TRY(h, "global_bundle_adjust(refuse)", msf::gba_refuse(call, cs.st));
+      if (h->h_gba_rec->malformed) return MSF_OK;   // as a malformed problem of msf_bundle_adjust_device: the status says it
+      return fail(h, MSF_ERR_CAPACITY, "msf_global_bundle_adjust_device: more than max_free_cams free cameras");
+    }
+    const int32_t stop_at_entry = h->h_gba_rec->stop;
+    if (int rc = carve(h, h->d_gba, (size_t)1 << 20, "hipMalloc(global bundle adjustment workspace)",
+                       [&](msf::Carver& c) { call.s = msf::gba::layout(c, nc, np, ne, n_free); }))
+      return rc;
+    int status = 0;
+    HIP_TRY(h, "global_bundle_adjust", msf::gba_solve(call, n_free, stop_at_entry, h->h_gba_rec, nullptr, cs.st, &status));
+    return MSF_OK;   // gba_solve has waited for the stream, whichever it is
   });
 }
 

@@ -135,7 +135,46 @@ MSF_HD void matrix_of(const Estimate& e, double* rt) {
   rt[8] = txz - twy, rt[9] = tyz + twx, rt[10] = 1 - (txx + tyy), rt[11] = e.t[2];
 }
 
-// SE3Quat::exp of dx = (omega, upsilon): r row-major 3 x 3, t = V upsilon
+// sin and cos of x >= 0 in plain f64 multiplies and adds, so that every build that keeps the order and does not fuse
+// (-ffp-contract=off) gives the same bits -- libm's sin and cos do not: a device's and a host's round some arguments
+// differently in the last bit.  Cody-Waite reduction by pi / 2 in three pieces (exact products for k < 2^20) and the
+// customary minimax polynomials on [-pi / 4, pi / 4]; within 1 ulp of the host's libm (tests/cpp/sin_cos_main.cpp).
+// Beyond 1e5 rad, and for what is not finite, libm's own (no step of an optimisation gets there, and no parity is
+// claimed).
+MSF_HD void sin_cos(double x, double* s, double* c) {
+  if (!(x <= 1e5)) {
+    *s = sin(x), *c = cos(x);
+    return;
+  }
+  double r = x;
+  long long k = 0;
+  if (x > 0.78539816339744828) {
+    k = (long long)(x * 6.36619772367581382433e-01 + 0.5);
+    const double fk = (double)k;
+    r = ((x - fk * 1.57079632673412561417e+00) - fk * 6.07710050630396597660e-11) - fk * 2.02226624871116645580e-21;
+  }
+  const double z = r * r;
+  const double ps = 8.33333333332248946124e-03 +
+                    z * (-1.98412698298579493134e-04 +
+                         z * (2.75573137070700676789e-06 + z * (-2.50507602534068634195e-08 + z * 1.58969099521155010221e-10)));
+  const double sr = r + (z * r) * (-1.66666666666666324348e-01 + z * ps);
+  const double pc = z * (4.16666666666666019037e-02 +
+                         z * (-1.38888888888741095749e-03 +
+                              z * (2.48015872894767294178e-05 +
+                                   z * (-2.75573143513906633035e-07 +
+                                        z * (2.08757232129817482790e-09 + z * -1.13596475577881948265e-11)))));
+  const double cr = 1.0 - (0.5 * z - z * pc);
+  switch (k & 3) {
+    case 0: *s = sr, *c = cr; break;
+    case 1: *s = cr, *c = -sr; break;
+    case 2: *s = -sr, *c = -cr; break;
+    default: *s = -cr, *c = sr; break;
+  }
+}
+
+// SE3Quat::exp of dx = (omega, upsilon): r row-major 3 x 3, t = V upsilon.  kOwnTrig: sin_cos() above instead of libm's
+// (the bundle adjustments, whose host build the device has to match bit for bit).
+template <bool kOwnTrig = false>
 MSF_HD void se3_exp(const double* dx, double* r, double* t) {
   const double a = dx[0], b = dx[1], c = dx[2];
   const double theta = sqrt(a * a + b * b + c * c);
@@ -146,7 +185,10 @@ MSF_HD void se3_exp(const double* dx, double* r, double* t) {
   if (theta < kSmallAngle) {
     kr1 = 1, kr2 = 1, kv1 = 1, kv2 = 1;
   } else {
-    const double s = sin(theta), co = cos(theta), th2 = theta * theta;
+    double s, co;
+    if (kOwnTrig) sin_cos(theta, &s, &co);
+    else s = sin(theta), co = cos(theta);
+    const double th2 = theta * theta;
     kr1 = s / theta, kr2 = (1 - co) / th2;
     kv1 = (1 - co) / th2, kv2 = (theta - s) / (th2 * theta);
   }
@@ -160,9 +202,10 @@ MSF_HD void se3_exp(const double* dx, double* r, double* t) {
 }
 
 // oplus: exp(dx) * e
+template <bool kOwnTrig = false>
 MSF_HD Estimate moved(const Estimate& e, const double* dx) {
   double r[9], t[3], d[4];
-  se3_exp(dx, r, t);
+  se3_exp<kOwnTrig>(dx, r, t);
   quaternion_of(r, 3, d);
   normalise_rotation(d);
   const double* q = e.q;

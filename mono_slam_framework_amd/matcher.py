@@ -617,6 +617,82 @@ class _Matcher:
                                                      C.byref(prm), C.byref(res), stream))
         return d
 
+    def global_bundle_adjust(self, cam_Tcw, cam_fixed, points, edge_cam, edge_point, edge_obs, K, schedule=(1, (10, 0), (0, 0)),
+                             stop=None, huber_delta2=5.991, chi2=5.991, diagnostics=True):
+        """Optimizer::GlobalBundleAdjustemnt (Optimizer.cc:62-69; the default schedule is the reference's call) on one
+        problem of up to 1024 free cameras, spread over the whole device: arguments and the returned dict as
+        bundle_adjust, bit for bit the same result wherever bundle_adjust takes the problem.  stop: None, an int, or an
+        int32 numpy array of one element that another thread may set while the call runs.  More than 1024 free cameras:
+        MsfError with code MSF_ERR_CAPACITY."""
+        tcw = np.ascontiguousarray(cam_Tcw, np.float32).reshape(-1, 12)
+        fixed = np.ascontiguousarray(cam_fixed, np.uint8).reshape(-1)
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        ec = np.ascontiguousarray(edge_cam, np.int32).reshape(-1)
+        ep = np.ascontiguousarray(edge_point, np.int32).reshape(-1)
+        obs = np.ascontiguousarray(edge_obs, np.float32).reshape(-1, 2)
+        nc, npt, ne = len(tcw), len(pts), len(ec)
+        assert len(fixed) == nc and len(ep) == ne and len(obs) == ne
+        d = {k: np.zeros(shape, dt) for k, (shape, dt) in _lib.ba_shapes(1, nc, npt, ne).items()}
+        if not diagnostics:
+            for name, _, per, _ in _lib.BA_ARRAYS:
+                if per.startswith("it"):
+                    del d[name]
+        res = _fill(_lib.BaResult(), d)
+        prm = self._ba_params(K, schedule, huber_delta2, chi2)
+        if stop is None or isinstance(stop, np.ndarray):
+            st = stop
+            assert st is None or (st.dtype == np.int32 and st.size == 1)
+        else:
+            st = np.array([stop], np.int32)
+        self._check(self._L.msf_global_bundle_adjust(self._h, nc, tcw.ctypes.data, fixed.ctypes.data, npt, pts.ctypes.data,
+                                                     ne, ec.ctypes.data, ep.ctypes.data, obs.ctypes.data,
+                                                     st.ctypes.data if st is not None else None, C.byref(prm), C.byref(res)))
+        out = dict(d)
+        out["status"] = int(d["status"][0])
+        out["round_iterations"] = d["round_iterations"][0]
+        for name, _, per, _ in _lib.BA_ARRAYS:
+            if name not in d:
+                continue
+            if per == "it":
+                out[name] = d[name][0]
+            elif per == "it_cam":
+                out[name] = d[name].reshape((_lib.BA_SLOTS, nc) + d[name].shape[1:])
+            elif per == "it_point":
+                out[name] = d[name].reshape((_lib.BA_SLOTS, npt) + d[name].shape[1:])
+        return out
+
+    def global_bundle_adjust_device(self, d_cam_Tcw, d_cam_fixed, d_points, d_edge_cam, d_edge_point, d_edge_obs, K,
+                                    schedule=(1, (10, 0), (0, 0)), max_free_cams=_lib.GBA_MAX_FREE_CAMS, d_stop=None,
+                                    huber_delta2=5.991, chi2=5.991, out=None, diagnostics=True, stream=None):
+        """The same with the problem in device memory (tensors as one problem of bundle_adjust_device, d_stop None or
+        an int32 tensor of one element).  -> dict of CUDA tensors named and shaped as _lib.ba_shapes(1, cams, points,
+        edges) says; without `diagnostics` no per-iteration arrays.  `out`: tensors to write into instead of fresh
+        zeros.  Enqueued on `stream`, but the host decides every trial: the call returns when the problem is finished."""
+        import torch
+        for t, dt in ((d_cam_Tcw, torch.float32), (d_cam_fixed, torch.uint8), (d_points, torch.float32),
+                      (d_edge_cam, torch.int32), (d_edge_point, torch.int32), (d_edge_obs, torch.float32)):
+            assert t.is_cuda and t.is_contiguous() and t.dtype == dt
+        cams, points, edges = d_cam_fixed.numel(), d_points.numel() // 3, d_edge_cam.numel()
+        assert d_cam_Tcw.numel() == cams * 12 and d_edge_point.numel() == edges and d_edge_obs.numel() == edges * 2
+        if d_stop is not None:
+            assert d_stop.is_cuda and d_stop.dtype == torch.int32 and d_stop.numel() == 1
+        d = out
+        if d is None:
+            z = _zeros_on(d_points.device)
+            d = {k: z(shape, dt) for k, (shape, dt) in _lib.ba_shapes(1, cams, points, edges).items()}
+            if not diagnostics:
+                for name, _, per, _ in _lib.BA_ARRAYS:
+                    if per.startswith("it"):
+                        del d[name]
+        res = _fill(_lib.BaResult(), d)
+        prm = self._ba_params(K, schedule, huber_delta2, chi2)
+        self._check(self._L.msf_global_bundle_adjust_device(self._h, cams, d_cam_Tcw.data_ptr(), d_cam_fixed.data_ptr(),
+                                                            points, d_points.data_ptr(), edges, d_edge_cam.data_ptr(),
+                                                            d_edge_point.data_ptr(), d_edge_obs.data_ptr(), max_free_cams,
+                                                            d_stop.data_ptr() if d_stop is not None else None,
+                                                            C.byref(prm), C.byref(res), stream))
+        return d
+
     def render_match_image(self, frame1, frame2, matches, has_mp1=None, has_mp2=None):
         """Tracking::CreateCurrentMatchImage (Tracking.cc:899-940) -> uint8 [H, 2W, 3]."""
         a, b = self._image(frame1), self._image(frame2)
