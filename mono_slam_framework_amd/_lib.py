@@ -1,4 +1,4 @@
-"""ctypes view of include/msf_abi.h, include/msf_initializer.h, include/msf_local_mapping.h, include/msf_pnp.h, include/msf_pose.h, include/msf_ba.h and include/msf_global_ba.h.  Loading fails loudly when libmsf.so is missing: there is no CPU fallback."""
+"""ctypes view of include/msf_abi.h, include/msf_initializer.h, include/msf_local_mapping.h, include/msf_pnp.h, include/msf_pose.h, include/msf_ba.h, include/msf_global_ba.h and include/msf_tracking.h.  Loading fails loudly when libmsf.so is missing: there is no CPU fallback."""
 import ctypes as C
 import os
 
@@ -65,6 +65,12 @@ BA_SYMBOLS = ["msf_ba_version", "msf_bundle_adjust", "msf_bundle_adjust_device"]
 GLOBAL_BA_SYMBOLS = ["msf_global_ba_version", "msf_global_ba_tile_rows", "msf_global_bundle_adjust",
                      "msf_global_bundle_adjust_device"]
 GBA_MAX_FREE_CAMS = 1024
+
+# every symbol include/msf_tracking.h declares (again a header and a version of its own)
+TRACKING_SYMBOLS = ["msf_tracking_version", "msf_frustum", "msf_frustum_device", "msf_claim_points_device",
+                    "msf_search_local_points"]
+MSF_POINT_BAD, MSF_POINT_SEEN = 1, 2
+MSF_SEARCH_KEEP_ON_DEVICE = 1
 
 
 class Config(C.Structure):
@@ -229,6 +235,56 @@ def ba_shapes(problems, cams, points, edges):
     return {name: (lead[per] + tuple(tail), dt) for name, dt, per, tail in BA_ARRAYS}
 
 
+class LocalMap(C.Structure):
+    """msf_local_map: host pointers for msf_frustum / msf_search_local_points, device pointers for the *_device calls"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_points", C.c_int32), ("n_kf", C.c_int32),
+                ("n_entries", C.c_int32), ("n_cur", C.c_int32), ("points", C.c_void_p), ("kf_start", C.c_void_p),
+                ("kf_key", C.c_void_p), ("kf_point", C.c_void_p), ("cur_key", C.c_void_p), ("cur_point", C.c_void_p)]
+
+
+class FrustumParams(C.Structure):
+    """msf_frustum_params: the current frame's view, camera centre, image bounds and viewing-cosine limit"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("view", View), ("Ow", C.c_float * 3),
+                ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float),
+                ("viewing_cos_limit", C.c_float)]
+
+
+class DeviceCorr(C.Structure):
+    """msf_device_corr: where msf_search_local_points left the correspondences with MSF_SEARCH_KEEP_ON_DEVICE"""
+    _fields_ = [("struct_size", C.c_uint32), ("corr_cap", C.c_int32), ("d_corr_p3d", C.c_void_p),
+                ("d_corr_p2d", C.c_void_p), ("d_corr_point", C.c_void_p), ("d_n_corr", C.c_void_p)]
+
+
+MAP_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("max_distance", "<f4"), ("flags", "<u4")])
+LOCAL_CLAIM_DTYPE = np.dtype([("key", "<i4"), ("point", "<i4"), ("kf", "<i4"), ("match", "<i4")])
+# msf_frustum_result's / msf_claim_result's arrays in declaration order: (name, dtype, per "call" / "point" / "kf" /
+# "corr", trailing shape; "cap" = the lists' stride); csrc/tracking_arrays.h holds the same tables
+# (tests/test_tracking_arrays_host.py compares them)
+FRUSTUM_ARRAYS = [("status_word", "int32", "call", ()), ("n_to_match", "int32", "kf", ()), ("status", "uint8", "point", ()),
+                  ("visible", "uint8", "point", ()), ("owner_kf", "int32", "point", ()), ("u", "float32", "point", ()),
+                  ("v", "float32", "point", ()), ("dist", "float32", "point", ()), ("view_cos", "float32", "point", ())]
+CLAIM_ARRAYS = [("status_word", "int32", "call", ()), ("n_claims", "int32", "call", ()), ("n_claimed", "int32", "kf", ()),
+                ("claims", LOCAL_CLAIM_DTYPE, "kf", ("cap",)), ("claim_status", "uint8", "kf", ("cap",)),
+                ("n_corr", "int32", "call", ()), ("corr_p3d", "float32", "corr", (3,)), ("corr_p2d", "float32", "corr", (2,)),
+                ("corr_point", "int32", "corr", ())]
+
+
+class FrustumResult(C.Structure):
+    """msf_frustum_result: host pointers for msf_frustum / msf_search_local_points, device pointers for msf_frustum_device"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(a[0], C.c_void_p) for a in FRUSTUM_ARRAYS]
+
+
+class ClaimResult(C.Structure):
+    """msf_claim_result: device pointers for msf_claim_points_device, host pointers for msf_search_local_points"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(a[0], C.c_void_p) for a in CLAIM_ARRAYS]
+
+
+def tracking_shapes(table, points, kfs, cap, corr_cap):
+    """-> {name: (shape, dtype)} of msf_frustum_result's (FRUSTUM_ARRAYS) or msf_claim_result's (CLAIM_ARRAYS) arrays"""
+    lead = {"call": (1,), "point": (points,), "kf": (kfs,), "corr": (corr_cap,)}
+    return {name: (lead[per] + tuple(cap if t == "cap" else t for t in tail), dt) for name, dt, per, tail in table}
+
+
 VIEW_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4")])
 MATCH_DTYPE = np.dtype([("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4")])
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("response", "<f4"), ("angle", "<f4"),
@@ -303,6 +359,12 @@ def load():
     L.msf_global_bundle_adjust.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, C.POINTER(BaParams), C.POINTER(BaResult)]
     L.msf_global_bundle_adjust_device.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, C.POINTER(BaParams),
                                                   C.POINTER(BaResult), vp]
+    L.msf_tracking_version.restype = C.c_int
+    L.msf_frustum.argtypes = [vp, C.POINTER(LocalMap), C.POINTER(FrustumParams), C.POINTER(FrustumResult)]
+    L.msf_frustum_device.argtypes = [vp, C.POINTER(LocalMap), C.POINTER(FrustumParams), C.POINTER(FrustumResult), vp]
+    L.msf_claim_points_device.argtypes = [vp, C.POINTER(LocalMap), vp, i32, vp, vp, i32, C.POINTER(ClaimResult), vp]
+    L.msf_search_local_points.argtypes = [vp, i32, vp, C.POINTER(LocalMap), C.POINTER(FrustumParams), C.c_uint32, vp, vp,
+                                          i32, C.POINTER(FrustumResult), C.POINTER(ClaimResult), C.POINTER(DeviceCorr)]
     L.msf_render_match_image.argtypes = [vp, C.POINTER(Image), C.POINTER(Image), vp, i32, vp, vp, vp, i64]
     L.msf_weights_info.argtypes = [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(i64)]
     L.msf_convert_weights.argtypes = [C.c_char_p, C.c_char_p]

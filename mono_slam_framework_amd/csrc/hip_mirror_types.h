@@ -1,5 +1,5 @@
 // hip_mirror_types.h -- what the header-only C++ mirrors (hip_initializer.h, hip_local_mapping.h, hip_pnp_solver.h,
-// hip_optimizer.h) share: the two point types and the zeroed, sized struct every C ABI call starts from.  No HIP and no
+// hip_optimizer.h, hip_tracking.h) share: the two point types and the zeroed, sized struct every C ABI call starts from.  No HIP and no
 // OpenCV in here.
 #pragma once
 

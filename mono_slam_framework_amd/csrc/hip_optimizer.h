@@ -110,6 +110,44 @@ class Optimizer {
     return true;
   }
 
+  // PoseOptimization of ONE list that is already in device memory -- d_p3d [cap][3], d_p2d [cap][2], its length at
+  // *d_n -- as msf_search_local_points leaves the correspondences of a tracked frame with MSF_SEARCH_KEEP_ON_DEVICE
+  // (hip_tracking.h: msf::TrackLocalMap).  Only the entry pose goes up and only the pose, the counts and the flags come
+  // back, through a block allocated here.  -> as PoseOptimization; -1 also for a list without a valid length (*d_n < 0).
+  static int PoseOptimizationDevice(msf_handle* handle, const float* d_p3d, const float* d_p2d, int32_t cap,
+                                    const int32_t* d_n, const float intrinsics[4], float Tcw[16],
+                                    std::vector<bool>& outliers, float chi2 = 5.991f) {
+    if (cap < 1) return -1;
+    struct View {
+      float* Tcw0;
+      size_t inputs_end;
+      msf_pose_result out;
+    };
+    DeviceBlock mem;
+    View dev, host;
+    const auto layout = [&](Carver& c) {
+      View v;
+      v.Tcw0 = c.take<float>(12);
+      v.inputs_end = c.off;
+      v.out = sized<msf_pose_result>();
+      v.out.n_good = c.take<int32_t>(1);
+      v.out.rounds_run = c.take<int32_t>(1);
+      v.out.n_edges = c.take<int32_t>(1);
+      v.out.Tcw = c.take<float>(12);
+      v.out.outliers = c.take<uint8_t>(cap);
+      return v;
+    };
+    if (!mem.place(layout, &dev, &host)) return -1;
+    std::memcpy(host.Tcw0, Tcw, 48);
+    const msf_pose_params prm = Params(intrinsics, chi2);
+    if (!mem.upload() ||
+        msf_pose_optimize_device(handle, 1, d_p3d, d_p2d, cap, d_n, dev.Tcw0, 12, nullptr, 0, &prm, &dev.out, nullptr) != MSF_OK ||
+        !mem.download() || host.out.n_good[0] < 0)
+      return -1;
+    Report(host.out.n_edges[0], host.out.outliers, host.out.rounds_run[0], host.out.Tcw, Tcw, outliers);
+    return host.out.n_good[0];
+  }
+
  private:
   static msf_pose_params Params(const float intrinsics[4], float chi2) {
     msf_pose_params prm = sized<msf_pose_params>();

@@ -393,6 +393,142 @@ class _Matcher:
             new.append(e)
         return num, out_lists, new
 
+    # --- Tracking::SearchLocalPoints (include/msf_tracking.h) --------------------------------------
+    _MAP_KEYS = ("points", "kf_start", "kf_key", "kf_point", "cur_key", "cur_point")
+
+    @staticmethod
+    def make_local_map(points, kf_start, kf_key, kf_point, cur_key=(), cur_point=()):
+        """-> the local map of one call as a dict of contiguous numpy arrays: points MAP_POINT_DTYPE [n_points],
+        kf_start int32 [n_kf + 1] (empty: no key frame), kf_key / kf_point int32 [n_entries], cur_key / cur_point
+        int32 [n_cur]"""
+        i32 = lambda a: np.ascontiguousarray(np.asarray(a, np.int32).reshape(-1))
+        return dict(points=np.ascontiguousarray(np.asarray(points, _lib.MAP_POINT_DTYPE).reshape(-1)),
+                    kf_start=i32(kf_start), kf_key=i32(kf_key), kf_point=i32(kf_point), cur_key=i32(cur_key),
+                    cur_point=i32(cur_point))
+
+    @staticmethod
+    def local_map_to_device(lmap, device="cuda"):
+        """a make_local_map dict -> the same with CUDA tensors (points as uint8 [n_points, 32])"""
+        import torch
+        out = {}
+        for k in _Matcher._MAP_KEYS:
+            a = lmap[k].view(np.uint8).reshape(-1, 32) if k == "points" else lmap[k]
+            out[k] = torch.from_numpy(a.copy()).to(device)
+        return out
+
+    @classmethod
+    def _local_map(cls, lmap):
+        """-> (msf_local_map over the dict's numpy arrays or CUDA tensors, n_points, n_kf)"""
+        ptr = lambda a: a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()
+        count = lambda a: a.size if isinstance(a, np.ndarray) else a.numel()
+        pts = lmap["points"]
+        n_points = pts.size if isinstance(pts, np.ndarray) else pts.numel() // 32
+        n_kf = max(count(lmap["kf_start"]) - 1, 0)
+        n_entries, n_cur = count(lmap["kf_key"]), count(lmap["cur_key"])
+        assert count(lmap["kf_point"]) == n_entries and count(lmap["cur_point"]) == n_cur
+        m = _lib.LocalMap(struct_size=C.sizeof(_lib.LocalMap), n_points=n_points, n_kf=n_kf, n_entries=n_entries,
+                          n_cur=n_cur, **{k: ptr(lmap[k]) for k in cls._MAP_KEYS})
+        return m, n_points, n_kf
+
+    @classmethod
+    def _frustum_params(cls, view, Ow, bounds, viewing_cos_limit):
+        v = cls.make_views(view if getattr(view, "dtype", None) == _lib.VIEW_DTYPE else [view])
+        prm = _lib.FrustumParams(struct_size=C.sizeof(_lib.FrustumParams), viewing_cos_limit=viewing_cos_limit)
+        C.memmove(C.byref(prm.view), v.ctypes.data, 64)
+        prm.Ow[:] = [float(x) for x in np.asarray(Ow, np.float32).reshape(3)]
+        prm.min_x, prm.max_x, prm.min_y, prm.max_y = [float(b) for b in bounds]
+        return prm
+
+    def frustum(self, lmap, view, Ow, bounds, viewing_cos_limit=0.5):
+        """Steps 1-2 of Tracking::SearchLocalPoints on a make_local_map dict: per point the owner key frame and
+        Frame::isInFrustum (Frame.cc:48-84) from the current frame's `view`, camera centre Ow and bounds = (mnMinX,
+        mnMaxX, mnMinY, mnMaxY).  -> dict of msf_frustum_result's arrays (status_word as an int)."""
+        m, n_points, n_kf = self._local_map(lmap)
+        d = {k: np.zeros(shape, dt) for k, (shape, dt) in _lib.tracking_shapes(_lib.FRUSTUM_ARRAYS, n_points, n_kf, 1, 0).items()}
+        res = _fill(_lib.FrustumResult(), d)
+        prm = self._frustum_params(view, Ow, bounds, viewing_cos_limit)
+        self._check(self._L.msf_frustum(self._h, C.byref(m), C.byref(prm), C.byref(res)))
+        d["status_word"] = int(d["status_word"][0])
+        return d
+
+    def frustum_device(self, d_lmap, view, Ow, bounds, viewing_cos_limit=0.5, out=None, stream=None):
+        """The same on a local_map_to_device dict.  -> dict of CUDA tensors named and shaped as msf_frustum_result says;
+        `out`: tensors to write into instead of fresh zeros.  Asynchronous on `stream` (None = handle stream + sync)."""
+        m, n_points, n_kf = self._local_map(d_lmap)
+        d = out
+        if d is None:
+            z = _zeros_on(d_lmap["points"].device)
+            d = {k: z(shape, dt) for k, (shape, dt) in _lib.tracking_shapes(_lib.FRUSTUM_ARRAYS, n_points, n_kf, 1, 0).items()}
+        res = _fill(_lib.FrustumResult(), d)
+        prm = self._frustum_params(view, Ow, bounds, viewing_cos_limit)
+        self._check(self._L.msf_frustum_device(self._h, C.byref(m), C.byref(prm), C.byref(res), stream))
+        return d
+
+    def claim_points_device(self, d_lmap, d_matches, d_n_out, d_matched, corr_cap, out=None, stream=None):
+        """Steps 4-5 on lists in device memory: d_matches int32 [n_kf, cap, 4], d_n_out int32 [n_kf], d_matched uint8
+        [n_kf] (the gate).  -> dict of CUDA tensors named as msf_claim_result says: claims int32 [n_kf * cap, 4] (key,
+        point, kf, match; the first n_claims), claim_status uint8 [n_kf, cap], corr_* [corr_cap, ...].  `out`: tensors
+        to write into instead of fresh zeros."""
+        import torch
+        m, n_points, n_kf = self._local_map(d_lmap)
+        cap = d_matches.shape[1]
+        assert d_matches.is_cuda and d_matches.is_contiguous() and d_matches.dtype == torch.int32
+        assert tuple(d_matches.shape) == (n_kf, cap, 4) and d_n_out.numel() == n_kf and d_matched.numel() == n_kf
+        assert d_n_out.dtype == torch.int32 and d_matched.dtype == torch.uint8
+        d = out
+        if d is None:
+            z = _zeros_on(d_lmap["points"].device)
+            d = {}
+            for k, (shape, dt) in _lib.tracking_shapes(_lib.CLAIM_ARRAYS, n_points, n_kf, cap, corr_cap).items():
+                d[k] = z((n_kf * cap, 4), "int32") if k == "claims" else z(shape, dt)
+        res = _fill(_lib.ClaimResult(), d)
+        self._check(self._L.msf_claim_points_device(self._h, C.byref(m), d_matches.data_ptr(), cap, d_n_out.data_ptr(),
+                                                    d_matched.data_ptr(), corr_cap, C.byref(res), stream))
+        return d
+
+    def search_local_points(self, query_slot, slots, lmap, view, Ow, bounds, viewing_cos_limit=0.5, cap=4096,
+                            keep_on_device=False, want_lists=True):
+        """Tracking::SearchLocalPoints' loop (Tracking.cc:594-632) in one call: the stored frame query_slot against the
+        stored frames `slots`, one per key frame of the make_local_map dict `lmap`.  -> dict: num_matches [n_kf]
+        (-1 for a key frame the gate left out), lists (or None), frustum (as frustum() returns it), n_claims,
+        n_claimed [n_kf], claims LOCAL_CLAIM_DTYPE [n_claims], claim_status [n_kf, cap], and the correspondences
+        n_corr, corr_p3d, corr_p2d, corr_point -- or with keep_on_device `keep`: (d_corr_p3d, d_corr_p2d, d_corr_point,
+        d_n_corr, corr_cap) as device addresses inside the handle's workspace, valid until the next call of this
+        family."""
+        slots = np.ascontiguousarray(np.asarray(slots, np.int32).reshape(-1))
+        m, n_points, n_kf = self._local_map(lmap)
+        if slots.size != n_kf:
+            raise ValueError("one slot per key frame")
+        corr_cap = m.n_cur + n_kf * cap
+        num = np.zeros(n_kf, np.int32)
+        lists = np.zeros((n_kf, cap), _lib.MATCH_DTYPE) if want_lists else None
+        fd = {k: np.zeros(shape, dt) for k, (shape, dt) in _lib.tracking_shapes(_lib.FRUSTUM_ARRAYS, n_points, n_kf, 1, 0).items()}
+        cd = {k: np.zeros(shape, dt) for k, (shape, dt) in _lib.tracking_shapes(_lib.CLAIM_ARRAYS, n_points, n_kf, cap, corr_cap).items()}
+        cd["claims"] = np.zeros(n_kf * cap, _lib.LOCAL_CLAIM_DTYPE)
+        if keep_on_device:
+            for k in ("corr_p3d", "corr_p2d", "corr_point"):
+                del cd[k]
+        fres, cres = _fill(_lib.FrustumResult(), fd), _fill(_lib.ClaimResult(), cd)
+        prm = self._frustum_params(view, Ow, bounds, viewing_cos_limit)
+        keep = _lib.DeviceCorr(struct_size=C.sizeof(_lib.DeviceCorr))
+        self._check(self._L.msf_search_local_points(
+            self._h, query_slot, slots.ctypes.data, C.byref(m), C.byref(prm),
+            _lib.MSF_SEARCH_KEEP_ON_DEVICE if keep_on_device else 0, num.ctypes.data,
+            lists.ctypes.data if want_lists else None, cap, C.byref(fres), C.byref(cres),
+            C.byref(keep) if keep_on_device else None))
+        fd["status_word"] = int(fd["status_word"][0])
+        n_claims, n_corr = int(cd["n_claims"][0]), int(cd["n_corr"][0])
+        out = dict(num_matches=num, lists=None, frustum=fd, n_claims=n_claims, n_claimed=cd["n_claimed"],
+                   claims=cd["claims"][:n_claims], claim_status=cd["claim_status"], n_corr=n_corr)
+        if want_lists:
+            out["lists"] = [lists[i, :min(max(int(num[i]), 0), cap)].view(np.int32).reshape(-1, 4).copy() for i in range(n_kf)]
+        if keep_on_device:
+            out["keep"] = (keep.d_corr_p3d, keep.d_corr_p2d, keep.d_corr_point, keep.d_n_corr, keep.corr_cap)
+        else:
+            k = max(n_corr, 0)
+            out.update(corr_p3d=cd["corr_p3d"][:k], corr_p2d=cd["corr_p2d"][:k], corr_point=cd["corr_point"][:k])
+        return out
+
     @staticmethod
     def _pnp_params(K, th2, min_inliers, n_iterations, max_records, seed):
         fx, fy, cx, cy = K
