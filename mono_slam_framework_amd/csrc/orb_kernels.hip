@@ -5,7 +5,7 @@
 // (src/featurematcher.cpp:10-45), whose arithmetic is cv::ORB::detectAndCompute
 // (cv::ORB::create() defaults) and BFMatcher(NORM_HAMMING)::knnMatch(k=2).
 //
-// Integer/byte work, HBM- and VALU-bound: no MFMA here.  This TU is compiled with
+// Integer/byte work, HBM- and VALU-bound; the one matrix product is k_describe's row blur.  This TU is compiled with
 // -ffp-contract=off so the few f32 steps (Harris response, fastAtan2, pattern rotation)
 // round exactly as the CPU restatement does.
 #include <type_traits>
@@ -15,6 +15,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "orb_blur_tiles.h"
 #include "orb_pattern.h"
 
 namespace msf {
@@ -1899,10 +1900,11 @@ __device__ __forceinline__ void det_sincosf(float t, float* s, float* c) {
 
 constexpr int PR = 22;             // patch radius: 19 (rotated pattern reach) + 3 (blur taps)
 constexpr int PD = 2 * PR + 1;     // 45
-constexpr int PP = 48;             // raw patch pitch
-constexpr int HP = 40;             // columns of the row-blurred patch
-constexpr int HC = 46;             // its column pitch in u16: 45 rows + 1; 92 B puts the ten column groups of a blur task on
-                                   // (nearly) distinct LDS banks (48 would put them all on one)
+constexpr int PP = blur_tiles::kRawPitch;   // raw patch pitch: columns cx - 24 .. cx + 23
+constexpr int HP = blur_tiles::kHbCols;     // columns of the row-blurred patch
+constexpr int HC = blur_tiles::kHbPitch;    // its column pitch in u16 (orb_blur_tiles.h)
+static_assert(PD == blur_tiles::kRawRows && PD * (PP / 4) == blur_tiles::kFetchLoads * blur_tiles::kFetchLanes, "patch fetch");
+typedef int v4i_t __attribute__((ext_vector_type(4)));
 
 // HALF_UP: the blur's column pass rounds half up (MSF_FLAG_BLUR_TIE_HALF_UP, and always with SUM256) instead of half to
 // even; SUM256: OpenCV's fixed-point kernel 18 34 48 56 48 34 18 instead of 18 34 49 55 49 34 18.  Compile-time: the
@@ -1910,16 +1912,29 @@ constexpr int HC = 46;             // its column pitch in u16: 45 rows + 1; 92 B
 template <bool HALF_UP, bool SUM256>
 __global__ __launch_bounds__(256) void k_describe(OrbGeometry g, FrameSrc src, const uint8_t* pyr,
                                                   msf_keypoint* kp, const uint32_t* kp_cnt, uint8_t* desc) {
-  __shared__ __attribute__((aligned(16))) uint8_t raw_s[4][PD * PP + 16];
+  // raw patch as p ^ 0x80 (the moments and the matrix operand both want p - 128 as a signed byte); 48 rows: the third row
+  // tile of the blur reads rows 45 .. 47 (and 16 B behind them), which nothing writes and no stored result depends on
+  __shared__ __attribute__((aligned(16))) uint8_t raw_s[4][blur_tiles::kRawBytes];
   // row-blurred patch, TRANSPOSED: column c (= sample x + 19) holds its 45 rows as consecutive u16 (pitch HC, even), so the
   // seven vertical taps of a sample are four consecutive dwords (two LDS reads instead of seven)
-  __shared__ __attribute__((aligned(16))) uint16_t hb_s[4][HP * HC];
+  __shared__ __attribute__((aligned(16))) uint16_t hb_s[4][blur_tiles::kHbEntries];
   __shared__ uint32_t disc_s[2 * kDiscTasks];
   // the rBRIEF table sits in LDS: read from constant memory per key point it is a VECTOR load behind the next patch's
   // prefetch, and waiting for it (vmcnt counts in order) waited for the prefetch too -- every key point then paid a full
   // memory latency (6 us per key point and wave; the kernel was bound by neither its bytes nor its instructions)
   __shared__ __attribute__((aligned(16))) int pat_s[256];
-  const int fi = blockIdx.y, slot = src.slot0 + fi;
+  // Which (frame, part) a workgroup takes.  Consecutive workgroups go to consecutive XCDs, each with an L2 of its own; with
+  // eight workgroups per frame (a big batch) the grid as it stands puts the eight parts of EVERY frame on eight XCDs, and
+  // the patches of a frame's key points -- neighbours in the (level, y, x) order overlap, and together the patches are
+  // about the frame's whole pyramid -- are fetched by eight L2s.  Within a group of eight frames the roles are swapped:
+  // workgroup (x, y) takes part y % 8 of frame 8 (y / 8) + x, so a frame stays on one XCD.  Speed only: any placement
+  // computes the same.  (The last frames of a call that are no full group keep the grid's own assignment.)
+  int fi = blockIdx.y, part = blockIdx.x;
+  if (gridDim.x == 8 && (fi | 7) < (int)gridDim.y) {
+    part = fi & 7;
+    fi = (fi & ~7) | (int)blockIdx.x;
+  }
+  const int slot = src.slot0 + fi;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;   // (scalar: key-point indices and record addresses are then scalar too)
   for (int i = threadIdx.x; i < 2 * kDiscTasks; i += 256) disc_s[i] = c_disc[i];
   pat_s[threadIdx.x] = reinterpret_cast<const int*>(c_pattern)[threadIdx.x];
@@ -1943,21 +1958,26 @@ __global__ __launch_bounds__(256) void k_describe(OrbGeometry g, FrameSrc src, c
   // Fetching the 45 x 48-byte patch is 63 % of this kernel when it is waited for (the patches of a batch amount to one
   // more read of the whole pyramid, at HBM speed): the patch of the wave's NEXT key point is requested into registers
   // before the current one is processed, and its position one key point earlier still.
-  constexpr int NPL = (PD * (PP / 4) + 63) / 64;          // dword loads per lane and patch
+  constexpr int NPL = blur_tiles::kFetchLoads;            // dword loads per lane and patch
   const uint32_t kstride = gridDim.x * 4;
-  uint32_t k = blockIdx.x * 4 + wave;
+  uint32_t k = (uint32_t)part * 4 + wave;
   uint32_t pre[NPL];
-  int xo_pre = 0;
-  // position (level, x, y) of key point k_ -> packed; patch loads of a packed position -> pre[], xo_pre
+  // position (level, x, y) of key point k_ -> packed; patch loads of a packed position -> pre[]
   auto meta = [&](uint32_t k_) -> uint3 {
     if (k_ >= count) return make_uint3(0u, 0u, 0u);
     const msf_keypoint* Kp = kp + (long long)slot * kKpCap + k_;
     return make_uint3((uint32_t)Kp->octave, (uint32_t)Kp->lx, (uint32_t)Kp->ly);
   };
-  // A wave walks ONE key point at a time: level and position are the same in every lane (they come from one address), and
-  // as scalars the patch is  s[base] + 32-bit lane offset  per load -- row r = i / 12 by a multiply-shift (exact for
-  // i < 576: 43691 = ceil(2^19 / 12)), offset r (pitch - 48) + 4 i.  (r04 formed r, the column and a 64-bit address per
-  // lane and load: 105 of the ~510 vector instructions per key point of a kernel that is 0.82 VALU-busy.)
+  // A wave walks ONE key point at a time: level and position are the same in every lane (they come from one address), so
+  // the patch is fetched at its BYTE address, columns cx - 24 .. cx + 23 of rows cy - 22 .. cy + 22 (key points sit >= 31
+  // px inside the level, so this never leaves the row): lane -> (row lane / 12 of five, dword lane % 12), nine loads
+  // each five rows further down.  The base and its steps of 5 pitch are scalar; per key point the lanes form one offset,
+  // row * pitch + 4 * dword.  The dwords are not 4-aligned in memory, which a global load takes; in LDS load u of a lane
+  // is dword 60 u + lane, and nothing has to be shifted into place afterwards.  Lanes 60 .. 63 repeat lane 59.
+  // (r05 fetched aligned dwords and shifted by cx % 4 in the moments and in every blur task; it formed a row by a
+  // multiply-shift and an offset per lane and LOAD.)
+  const int fl = blur_tiles::fetch_lane(lane);
+  const uint32_t fetch_row = (uint32_t)blur_tiles::fetch_row(lane), fetch_x4 = 4u * (uint32_t)blur_tiles::fetch_dword(lane);
   auto issue = [&](uint3 m) {
     const uint32_t lv = (uint32_t)__builtin_amdgcn_readfirstlane((int)m.x);
     const int mx = __builtin_amdgcn_readfirstlane((int)m.y), my = __builtin_amdgcn_readfirstlane((int)m.z);
@@ -1966,28 +1986,28 @@ __global__ __launch_bounds__(256) void k_describe(OrbGeometry g, FrameSrc src, c
     const unsigned long long img_ = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(b64 >> 32)) << 32) |
                                     (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b64);
     typedef const __attribute__((address_space(1))) uint8_t* gptr_t;   // global, not generic: a flat load counts as an LDS op too
-    // raw patch, radius 22, fetched as aligned dwords: columns ax .. ax+47 hold x = cx-22 .. cx+22 at byte
-    // offset xo (keypoints sit >= 31 px inside the level, so this never leaves the row)
-    const int ax = (mx - PR) & ~3;
-    xo_pre = (mx - PR) - ax;
-    gptr_t base = (gptr_t)(img_ + (unsigned long long)((long long)(my - PR) * (long long)pitch_ + ax));
-    const uint32_t pm = pitch_ - (uint32_t)PP;
+    const unsigned long long base = img_ + (unsigned long long)((long long)(my - PR) * (long long)pitch_ + (mx - PP / 2));
+    const uint32_t off = mad_u24(fetch_row, pitch_, fetch_x4);
 #pragma unroll
-    for (int u = 0; u < NPL; u++) {
-      const uint32_t i = (uint32_t)lane + 64u * (uint32_t)u;
-      const uint32_t r = (i * 43691u) >> 19;
-      const uint32_t off = mad_u24(r, pm, 4u * i);
-      pre[u] = i < (uint32_t)(PD * (PP / 4)) ? *(const __attribute__((address_space(1))) uint32_t*)(base + off) : 0u;
-    }
+    for (int u = 0; u < NPL; u++)
+      pre[u] = *(const __attribute__((address_space(1))) uint32_t*)((gptr_t)(base + (unsigned long long)(5u * (uint32_t)u * pitch_)) + off);
   };
-  // row blur: lane -> (row pair rl within a block of six, column group gq); dword offsets of its reads and writes
-  uint32_t* hb32 = reinterpret_cast<uint32_t*>(hb);
-  const int blur_rl = (lane * 26) >> 8, blur_gq = lane - 10 * blur_rl;       // lane / 10, lane % 10 (lanes 60..63: 6, 0..3)
-  const int blur_rd = blur_rl * (2 * (PP / 4)) + blur_gq, blur_wr = blur_gq * (4 * (HC / 2)) + blur_rl;
-  const bool blur_last = 18 + blur_rl < 23;                                    // pass 3 holds row pairs 18 .. 24
+  // row blur (orb_blur_tiles.h): byte address of this lane's A operand in row tile 0, its B operands (constant: the banded
+  // tap matrix, 12 registers for the three column tiles), and the byte address of its results of tile (0, 0) in hb
+  const uint32_t raw_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)raw;
+  const uint32_t hb_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint16_t*)hb;
+  const uint32_t blur_a = (uint32_t)blur_tiles::a_byte_offset(0, lane);
+  const uint32_t blur_w = (uint32_t)blur_tiles::hb_store_byte_offset(0, 0, lane);
+  v4i_t blur_b[blur_tiles::kTilesN];
+#pragma unroll
+  for (int nt = 0; nt < blur_tiles::kTilesN; nt++)
+#pragma unroll
+    for (int d = 0; d < 4; d++) blur_b[nt][d] = (int)blur_tiles::b_dword(SUM256, nt, lane, d);
+  const bool blur_cols = (lane & 15) < HP - 32;          // column tile 2 holds columns 32 .. 47: only 32 .. 39 are stored
+  const bool blur_rows = (lane >> 4) < 3;                // row tile 2, lanes 48 .. 63: rows 44 .. 47, only 44 | 45 are stored
   // descriptor samples: LDS byte address of hb[19][19 - 3], minus what the magic-constant sums carry (see there)
-  const uint32_t samp_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint16_t*)hb +
-                             2u * (uint32_t)((PR - 3) * HC + (PR - 3)) - 2u * HC * 0x400000u - 2u * 0x4B400000u;
+  static_assert(blur_tiles::kSampleReach == PR - 3, "the blur's three taps on either side of the pattern's reach");
+  const uint32_t samp_base = hb_lds + (uint32_t)blur_tiles::samp_byte_offset(0, 0) - 2u * HC * 0x400000u - 2u * 0x4B400000u;
   uint3 m_cur = meta(k), m_next = meta(k + kstride);
   if (k < count) issue(m_cur);
   for (; k < count; k += kstride) {
@@ -1995,12 +2015,8 @@ __global__ __launch_bounds__(256) void k_describe(OrbGeometry g, FrameSrc src, c
     msf_keypoint* K = kp + (long long)slot * kKpCap + k;
     const int l = (int)m_cur.x, cx = (int)m_cur.y, cy = (int)m_cur.z;
     (void)l; (void)cx; (void)cy;
-    const int xo = xo_pre;
 #pragma unroll
-    for (int u = 0; u < NPL; u++) {
-      const int i = lane + 64 * u;
-      if (i < PD * (PP / 4)) raw32[i] = pre[u];
-    }
+    for (int u = 0; u < NPL; u++) raw32[60 * u + fl] = pre[u] ^ 0x80808080u;     // (lanes 60 .. 63: lane 59's value again)
     m_cur = m_next;
     if (k + kstride < count) issue(m_cur);          // next patch: in flight while this key point is processed
     m_next = meta(k + 2 * kstride);
@@ -2012,15 +2028,12 @@ __global__ __launch_bounds__(256) void k_describe(OrbGeometry g, FrameSrc src, c
       // the u weights of a whole row sum to 0) and m01 += v * dot4(p, membership).  4 passes of the wave.
       int m10 = 0, m01 = 0;
       {
-        // pixel (u, v) sits at byte xo + 22 + u of raw row 22 + v; the windows start at u = -16 + 4k
-        const int dw0 = 1 + ((xo + 2) >> 2);
-        const uint32_t shf = (uint32_t)(xo + 2) & 3u;
+        // pixel (u, v) sits at byte 24 + u of raw row 22 + v; the windows start at u = -16 + 4k: dword 2 + k
 #pragma unroll
         for (int it = 0; it < kDiscTasks / 64; it++) {
           const int t = it * 64 + lane;
           const int row = t >> 3, k = t & 7;              // row = v + 15 (rows 31 are padding: zero weights); row + 7 <= 38
-          const uint32_t* d = raw32 + (row + 7) * (PP / 4) + dw0 + k;
-          const uint32_t pxw = __builtin_amdgcn_alignbyte(d[1], d[0], shf) ^ 0x80808080u;
+          const uint32_t pxw = raw32[(row + 7) * (PP / 4) + 2 + k];   // p ^ 0x80 already
           const uint32_t wu = disc_s[2 * t], wv = disc_s[2 * t + 1];
           // both moments as signed dot products of p - 128 with the byte weights u and v (0 outside the disc): the -128
           // cancels over a row for m10 (the u of a row sum to 0) and over the disc for m01 (rows v and -v are equally long)
@@ -2033,39 +2046,38 @@ __global__ __launch_bounds__(256) void k_describe(OrbGeometry g, FrameSrc src, c
       m01 = (int)__builtin_amdgcn_readlane((int)wave_incl_scan((uint32_t)m01), 63);
       angle = fast_atan2_deg((float)m01, (float)m10);
       // 7-tap row pass of GaussianBlur(7x7, sigma 2) in its 8u integer form (18 34 49 55 49 34 18, or OpenCV's bit-exact
-      // fixed-point kernel 18 34 48 56 48 34 18).  A task = TWO rows x 4 output columns from 2 x 4 aligned dwords: output j
-      // is the taps laid over bytes j .. j + 6 of the 12-byte window, i.e. v_dot4_u32_u8 of each window dword with the
-      // taps SHIFTED into place (10 dot products per 4 outputs, no per-output byte alignment).  Lane -> (row pair within a
-      // block of six, column group), so every LDS address of the four passes is lane base + immediate.
+      // fixed-point kernel 18 34 48 56 48 34 18): hb[c][r] = sum_j T[j] raw[r][c + 2 + j] is the product of the patch
+      // (rows x raw bytes) with a constant banded matrix, on the matrix pipe as 3 x 3 tiles of v_mfma_i32_16x16x64_i8.
+      // The operand bytes are p - 128 and the accumulators start at 128 sum(T), so the sums are the unsigned ones
+      // exactly.  A: one 16-byte LDS read per row tile, lane -> (row lane % 16, bytes 16 (lane / 16) ..); bytes 48 .. 63
+      // are the next row's and meet weight 0.  A lane's four results are rows 4 (lane / 16) .. + 3 of column lane % 16:
+      // two u16 pairs, one 8-byte store into the transposed image.  Layout, operand rule and model: orb_blur_tiles.h.
+      // (r05: shifted-tap v_dot4_u32_u8, 10 per 4 outputs, on 2 x 4 dwords shifted into place: ~160 vector and 48 LDS
+      // instructions per key point.)
       {
-        constexpr uint32_t T0 = 18, T1 = 34, T2 = SUM256 ? 48 : 49, T3 = SUM256 ? 56 : 55;      // taps T0 T1 T2 T3 T2 T1 T0
-        constexpr uint32_t A0 = T0 | T1 << 8 | T2 << 16 | T3 << 24, B0 = T2 | T1 << 8 | T0 << 16;
-        constexpr uint32_t A1 = T0 << 8 | T1 << 16 | T2 << 24, B1 = T3 | T2 << 8 | T1 << 16 | T0 << 24;
-        constexpr uint32_t A2 = T0 << 16 | T1 << 24, B2 = T2 | T3 << 8 | T2 << 16 | T1 << 24, C2 = T0;
-        constexpr uint32_t A3 = T0 << 24, B3 = T1 | T2 << 8 | T3 << 16 | T2 << 24, C3 = T1 | T0 << 8;
-        auto row4 = [&](const uint32_t* d, uint32_t* o) {
-          const uint32_t d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3];
-          const uint32_t e0 = __builtin_amdgcn_alignbyte(d1, d0, xo), e1 = __builtin_amdgcn_alignbyte(d2, d1, xo);
-          const uint32_t e2 = __builtin_amdgcn_alignbyte(d3, d2, xo);
-          o[0] = __builtin_amdgcn_udot4(e0, A0, __builtin_amdgcn_udot4(e1, B0, 0u, false), false);
-          o[1] = __builtin_amdgcn_udot4(e0, A1, __builtin_amdgcn_udot4(e1, B1, 0u, false), false);
-          o[2] = __builtin_amdgcn_udot4(e0, A2, __builtin_amdgcn_udot4(e1, B2, __builtin_amdgcn_udot4(e2, C2, 0u, false), false), false);
-          o[3] = __builtin_amdgcn_udot4(e0, A3, __builtin_amdgcn_udot4(e1, B3, __builtin_amdgcn_udot4(e2, C3, 0u, false), false), false);
-        };
-        // 23 row pairs (rows 0 .. 45; row 45 is the pad row of hb and reads the 16 spare bytes behind the raw patch and
-        // whatever follows them -- never sampled) x 10 column groups = 4 passes of 60 lanes; lanes 60 .. 63 repeat what
-        // lanes 0 .. 3 do in the next pass (same values to the same place) except in the last pass, where lanes with
-        // row pair >= 23 must not write
+        typedef __attribute__((address_space(3))) const v4i_t* lds_v4_t;
+        typedef uint32_t v2u_t __attribute__((ext_vector_type(2)));
+        typedef __attribute__((address_space(3))) v2u_t* lds_u2_t;
+        typedef __attribute__((address_space(3))) uint32_t* lds_u1_t;
+        constexpr int C0 = blur_tiles::acc_init(SUM256);
+        const v4i_t c0 = {C0, C0, C0, C0};
 #pragma unroll
-        for (int it = 0; it < 4; it++) {
-          const uint32_t* d = raw32 + blur_rd + it * (12 * (PP / 4));
-          uint32_t ou[4], ol[4];
-          row4(d, ou);
-          row4(d + PP / 4, ol);
-          if (it < 3 || blur_last) {
-            uint32_t* w = hb32 + blur_wr + it * 6;
+        for (int mt = 0; mt < blur_tiles::kTilesM; mt++) {
+          const v4i_t av = *(lds_v4_t)(uintptr_t)(raw_lds + blur_a + (uint32_t)(16 * mt * PP));
 #pragma unroll
-            for (int j = 0; j < 4; j++) w[j * (HC / 2)] = ou[j] | (ol[j] << 16);     // each <= 255 * 257 = 65535
+          for (int nt = 0; nt < blur_tiles::kTilesN; nt++) {
+            const v4i_t dv = __builtin_amdgcn_mfma_i32_16x16x64_i8(av, blur_b[nt], c0, 0, 0, 0);
+            const uint32_t wa = hb_lds + blur_w + (uint32_t)(2 * (16 * nt * HC + 16 * mt));
+            // each in-range result is <= 255 * 257 = 65535; what rows >= 45 give is shifted out or never stored
+            // (v_perm: the low halves of two registers side by side, blur_tiles::pack2 in one instruction)
+            const uint32_t lo = __builtin_amdgcn_perm((uint32_t)dv[1], (uint32_t)dv[0], 0x05040100u);
+            const uint32_t hi = __builtin_amdgcn_perm((uint32_t)dv[3], (uint32_t)dv[2], 0x05040100u);
+            if (mt < 2) {
+              if (nt < 2 || blur_cols) *(lds_u2_t)(uintptr_t)wa = v2u_t{lo, hi};
+            } else if (nt < 2 || blur_cols) {
+              if (blur_rows) *(lds_u2_t)(uintptr_t)wa = v2u_t{lo, hi};
+              else *(lds_u1_t)(uintptr_t)wa = lo;                      // rows 44 | 45; 46 and 47 are not stored
+            }
           }
         }
       }
