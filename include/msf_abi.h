@@ -364,8 +364,9 @@ int msf_gather_matches_device(msf_gather* g, const msf_match* d_packed, const in
  * workgroup index (orb_kernels.hip, k_walk).  That is live as long as the hardware starts workgroups of a grid in index
  * order -- observed on gfx950, not promised by HIP -- so every wait is bounded (2^19 polls, about one second).  A unit
  * that gives up flags its frame: the pairs of that frame come back with n_out = -1 and the call returns MSF_ERR_CAPACITY
- * like any other per-pair failure (never a silent wrong list); every other waiter of the launch leaves at once, the grid
- * drains.  The stall is counted in a device word that is never cleared; the next extraction that finds it non-zero
+ * like any other per-pair failure (never a silent wrong list).  A finish unit (the unit that cuts a level's candidate
+ * list and scores it inside the launch) that gives up flags its frame like any other unit.  Every other waiter of the
+ * launch leaves at once, the grid drains.  The stall is counted in a device word that is never cleared; the next extraction that finds it non-zero
  * switches the handle to one launch per level for the rest of its life (no in-launch waits; about 9 % slower at
  * 1280x720), and msf_last_error carries a note once.  MSF_DBG_WALK_MODE reports both.  Two handles extracting at the same
  * time on one device (msf_multi shards, per-size handles, a gather stream) do not stall each other: every grid's own
@@ -392,9 +393,13 @@ typedef enum msf_debug_what {
                                 `level` + 1: [8][240][320], [16][120][160], [32][60][80], [32][30][40] (level 0..3) */
   MSF_DBG_LOFTR_TOK = 11,    /* float [2][1200][32] tokens of pair 0 before the transformer (backbone + positional
                                 encoding) of the last match call; MSF_FLAG_KEEP_DEBUG handles only */
-  MSF_DBG_ORB_MATCH_FORM = 12 /* ORB, int32 [2]: {the Hamming 2-NN kernel of the handle's last match launch: 0 none yet,
+  MSF_DBG_ORB_MATCH_FORM = 12, /* ORB, int32 [2]: {the Hamming 2-NN kernel of the handle's last match launch: 0 none yet,
                                 1 k_match_split (32 workgroups per pair; calls of at most 128 pairs), 2 k_match (one
                                 workgroup per pair); the train chunk in effect (1024, or MSF_ORB_TRAIN_CHUNK)} */
+  MSF_DBG_WALK_FINISHED = 13 /* ORB, int32 [1] of slot: bit l set if level l's completeness check, retainBest(2N) cut and
+                                Harris responses were done by a finish unit inside the last extraction's walker launch
+                                (0 for every level of a dense, per-level or unfused call, with MSF_ORB_WALK_FINISH=0, and
+                                for a level that went to the dense second pass) */
 } msf_debug_what;
 /* copies to host; *n_bytes = bytes available (may exceed cap_bytes, then only cap_bytes are written) */
 int msf_debug_get(msf_handle* h, int32_t what, int32_t slot, int32_t level,

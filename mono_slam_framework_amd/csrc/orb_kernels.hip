@@ -546,9 +546,12 @@ constexpr int kTauBins = 64;             // score histogram bins of width 4 (the
 //   kQDone    strips of the quarter that are done (their histogram adds included)
 //   kQTau     the threshold in force: the largest refined threshold any strip published (atomicMax; 0 = none yet)
 //   kQFirst   kQReady | the first estimate, stored by the (frame, level)'s threshold unit once the level exists
-//   kQAll     strips of the level that are done: at wk_nx * wk_ny every pixel of level l + 1 has been written
-constexpr int kQDone = kTauBins, kQTau = kTauBins + 1, kQFirst = kTauBins + 2, kQAll = kTauBins + 3;
-constexpr int kQStat = kTauBins + 4;
+//   kQAll     strips of the level that are done: at wk_nx * wk_ny every pixel of level l + 1 has been written and every
+//             candidate of level l is in its list
+//   kQFin     1 once the (frame, level)'s finish unit has left its stage-1 list and Harris responses (finish_unit): the
+//             launches behind the walker skip it
+constexpr int kQDone = kTauBins, kQTau = kTauBins + 1, kQFirst = kTauBins + 2, kQAll = kTauBins + 3, kQFin = kTauBins + 4;
+constexpr int kQStat = kTauBins + 8;     // (a multiple of 4 words: the state of a (slot, level) starts 16-byte aligned)
 constexpr uint32_t kQReady = 0x80000000u;
 constexpr int RK = 16;                   // ring rows (power of two)
 // (kWkMaxPx, kWkMaxRows, the strip heights and kTauSites: orb_plan.h)
@@ -606,11 +609,14 @@ __device__ __forceinline__ int stream_score(const uint8_t* ring, uint32_t r0, ui
 // strip; a unit is a workgroup of one wave.  Workgroups b, b + 8, ... share an XCD (observed placement, speed only): XCD
 // x takes the frames [x n / 8, (x + 1) n / 8) and walks, level by level, first the threshold units of its frames, then
 // the sampled quarter of all their strips (strip index a multiple of 4), then the rest -- so the lines neighbouring
-// strips share stay in one L2, and whatever a unit needs was started long before it.
+// strips share stay in one L2, and whatever a unit needs was started long before it.  The launch over all levels also
+// holds a FINISH unit per (frame, level) (finish_unit: the level's completeness check, retainBest(2N) cut and Harris
+// responses), directly behind the threshold units of the next level.  The order itself: walk_unit, orb_plan.h.
 // Dependencies (chain = 1: the walker of level l - 1 makes level l):
 //   threshold unit (f, l), l > 0 : all strips of (f, l - 1) done            (kQAll of level l - 1: level l exists)
 //   strip of (f, l)              : the threshold of (f, l) published         (kQFirst; implies the line above)
 //   non-quarter strip, dyn       : the quarter of (f, l) done                (kQDone: the refined threshold)
+//   finish unit (f, l)           : all strips of (f, l) done                  (kQAll of level l)
 // Every wait is for units with a LOWER flat workgroup index, so with workgroups started in index order the lowest
 // unfinished one never waits and the launch drains; the waits are bounded all the same (kSpinMax polls of ~2 us): a unit
 // that gives up flags its frame (status, surfaced as n_out = -1), raises the launch's abort word -- every other waiter
@@ -623,6 +629,10 @@ constexpr uint32_t kSpinMax = 1u << 19;
 
 __device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// (a write-through store: the word is in memory, not a dirty line of this XCD's L2, whichever unit stores to it next)
+__device__ __forceinline__ void st_agent(uint32_t* p, uint32_t v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 // a unit gives up: its frame has no valid result, every waiter of the launch leaves
 __device__ __forceinline__ void unit_stall(uint32_t* status, int slot, uint32_t* abort_word, int lane) {
@@ -862,8 +872,10 @@ __device__ __forceinline__ void walk_strip(StreamSmem& sm, const OrbGeometry& g,
     for (uint32_t i = lane; i < nO; i += 64) {
       const uint32_t pk = sm.opk[i], sc_ = pk >> 16;
       if (base + i < out_cap) {
-        outk[base + i] = ((uint32_t)(y0 + (int)((pk >> 8) & 255u)) << 16) | (uint32_t)(xs + (int)(pk & 255u));
-        outs[base + i] = (uint8_t)sc_;
+        // write-through (agent-scope atomic stores): in memory, whichever XCD the level's finish unit runs on, once this
+        // strip has drained its stores and counted itself done
+        st_agent(&outk[base + i], ((uint32_t)(y0 + (int)((pk >> 8) & 255u)) << 16) | (uint32_t)(xs + (int)(pk & 255u)));
+        __hip_atomic_store(&outs[base + i], (uint8_t)sc_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       if (count_me) atomicAdd(&qs[sc_ >> 2], 1u);     // the quarter's exact scores: what the other strips refine tau from
     }
@@ -1187,14 +1199,16 @@ __device__ __forceinline__ void walk_strip(StreamSmem& sm, const OrbGeometry& g,
 #undef RZ_HSUM
 #undef RZ_EMIT
   }
-  if (count_me || RESIZE) {
+  {
     // Every store of this strip has left the wave's queue before the strip counts as done: the write-through stores of
-    // level l + 1's pixels are then in memory (what the next level's units wait for) and the histogram adds have been
-    // performed (agent-scope atomics both sides).  Inline asm: the compiler may not drop or move this wait.
+    // level l + 1's pixels and of this strip's candidates are then in memory (what the next level's units and this
+    // level's finish unit wait for) and the histogram adds and the threshold's atomic max have been performed
+    // (agent-scope atomics both sides).  Inline asm: the compiler may not drop or move this wait.  Every strip of every
+    // level counts, whether it makes a level or not (a strip that gave up a wait has returned above and does not).
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (lane == 0) {
       if (count_me) atomicAdd(&qs[kQDone], 1u);
-      if (RESIZE) atomicAdd(&qs[kQAll], 1u);
+      atomicAdd(&qs[kQAll], 1u);
     }
   }
 }
@@ -1406,13 +1420,268 @@ __device__ __forceinline__ void tau_unit(TauSmem& T, const OrbGeometry& g, const
     MSF_WAVE_SYNC();                                         // the LDS block is the next unit's
   }
   if (lane == 0) {
-    tau[idx] = (uint32_t)tv;
-    tau_first[idx] = (uint32_t)tv;
+    st_agent(&tau[idx], (uint32_t)tv);         // (the level's finish unit stores to both again)
+    st_agent(&tau_first[idx], (uint32_t)tv);
     // nothing to gain from a threshold: straight to the dense pass
     if (tv <= kFastT && L.tiles_x > 0) redo_list[atomicAdd(redo_cnt, 1u)] = (uint32_t)(fi * kOrbLevels + l);
     // the strips of this (frame, level) start from here
     __hip_atomic_store(&qs[kQFirst], kQReady | (uint32_t)tv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+}
+
+// ------------------------------------------------------------------ K5+K6: retainBest(2N) by FAST score, Harris response
+// HarrisResponses (orb.cpp), blockSize 7, k = 0.04, on the unblurred level.
+// One lane per candidate.  The 9 x 9 neighbourhood comes in as 27 aligned dwords (3 per row; scattered byte loads --
+// ~190 per candidate -- made the texture addresser the bottleneck: 0.67 ms of this stage per 2048 frames), and the
+// Sobel sums are separable dot products on bytes biased by 128 (differences and the 1-2-1 sums of differences are
+// unaffected by the bias):  G[row][j] = p[j+1] - p[j-1],  H[row][j] = p[j-1] + 2 p[j] + p[j+1] - 512,
+//   Ix[r][j] = G[r-1][j] + 2 G[r][j] + G[r+1][j],   Iy[r][j] = H[r+1][j] - H[r-1][j]   (all int32, exact).
+// RG: rows requested together.  9 (the selection kernels): all 27 loads in flight at once; 3 (a finish unit of the
+// walker launch, which must stay inside the walker's register budget): three groups of 9 loads -- the sums are integers,
+// the result is the same bit for bit.
+template <int RG = 9>
+__device__ __forceinline__ float harris_at(const uint8_t* img, int step, int x0, int y0) {
+  static_assert(9 % RG == 0, "whole groups of rows");
+  const int xb = (x0 - 4) & ~3;
+  const uint32_t o = (uint32_t)(x0 - 4) & 3u;
+  const uint8_t* base = img + (long long)(y0 - 4) * step + xb;
+  constexpr int kWG = 0x000100FF;                                 // weights (-1, 0, +1, 0) on bytes 0..3
+  constexpr int kWH = 0x00010201;                                 // weights ( 1, 2,  1, 0)
+  int Gm2[7], Gm1[7], Hm2[7], Hm1[7];
+  int a = 0, b = 0, c = 0;
+  // one row of the neighbourhood: its three dwords in, the sums of the 7 x 7 block's row t - 1 added
+  auto row = [&](const int t, const uint32_t r0, const uint32_t r1, const uint32_t r2) __attribute__((always_inline)) {
+    const uint32_t d0 = r0 ^ 0x80808080u, d1 = r1 ^ 0x80808080u, d2 = r2 ^ 0x80808080u;
+    const uint32_t w0 = __builtin_amdgcn_alignbyte(d1, d0, o);   // px -4 .. -1 (relative to x0)
+    const uint32_t w1 = __builtin_amdgcn_alignbyte(d2, d1, o);   // px  0 ..  3
+    const uint32_t w2 = d2 >> (8u * o);                          // px  4 in byte 0
+    // windows starting at px j-1 for j = -3 .. 3 (the 4th byte has weight 0)
+    const uint32_t win[7] = {w0, __builtin_amdgcn_alignbyte(w1, w0, 1), __builtin_amdgcn_alignbyte(w1, w0, 2),
+                             __builtin_amdgcn_alignbyte(w1, w0, 3), w1, __builtin_amdgcn_alignbyte(w2, w1, 1),
+                             __builtin_amdgcn_alignbyte(w2, w1, 2)};
+    int G[7], H[7];
+#pragma unroll
+    for (int j = 0; j < 7; j++) {
+      G[j] = __builtin_amdgcn_sdot4((int)win[j], kWG, 0, false);
+      H[j] = __builtin_amdgcn_sdot4((int)win[j], kWH, 0, false);
+    }
+    if (t >= 2) {
+#pragma unroll
+      for (int j = 0; j < 7; j++) {
+        const int Ix = Gm2[j] + 2 * Gm1[j] + G[j];
+        const int Iy = H[j] - Hm2[j];
+        a += Ix * Ix;
+        b += Iy * Iy;
+        c += Ix * Iy;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 7; j++) { Gm2[j] = Gm1[j]; Gm1[j] = G[j]; Hm2[j] = Hm1[j]; Hm1[j] = H[j]; }
+  };
+  if (RG == 9) {
+#pragma unroll
+    for (int t = 0; t < 9; t++) {
+      const uint32_t* rp = reinterpret_cast<const uint32_t*>(base + (long long)t * step);
+      row(t, rp[0], rp[1], rp[2]);
+    }
+  } else {
+    // the next group's addresses go through an empty asm that takes this group's sums: its loads cannot be requested
+    // before those sums exist, so only RG rows are held in registers at a time
+    uint32_t step_g = (uint32_t)step;
+#pragma unroll
+    for (int t0 = 0; t0 < 9; t0 += RG) {
+      uint32_t ld[RG][3];
+#pragma unroll
+      for (int u = 0; u < RG; u++) {
+        const uint32_t* rp = reinterpret_cast<const uint32_t*>(base + (unsigned long long)((uint32_t)(t0 + u) * step_g));
+        ld[u][0] = rp[0]; ld[u][1] = rp[1]; ld[u][2] = rp[2];
+      }
+#pragma unroll
+      for (int u = 0; u < RG; u++) row(t0 + u, ld[u][0], ld[u][1], ld[u][2]);
+      asm volatile("" : "+v"(step_g) : "v"(a), "v"(b), "v"(c), "v"(Gm1[0]), "v"(Hm1[0]));
+    }
+  }
+  const float scale = 1.f / ((1 << 2) * 7 * 255.f);
+  const float scale_sq_sq = scale * scale * scale * scale;
+  const float fa = (float)a, fb = (float)b, fc = (float)c;
+  return (fa * fb - fc * fc - 0.04f * (fa + fb) * (fa + fb)) * scale_sq_sq;
+}
+
+// entries of a score list at or above T: one wave, 16 scores per lane and load (bytes past n inside the last group are
+// stale and masked by index); the sum in every lane
+__device__ __forceinline__ uint32_t count_scores_from(const uint8_t* scs, uint32_t n, uint32_t T, int lane) {
+  uint32_t found = 0;
+  for (uint32_t i = 16u * lane; i < n; i += 16u * 64u) {
+    const uint4 v = *reinterpret_cast<const uint4*>(scs + i);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int b = 0; b < 16; b++)
+      if (i + b < n && ((w[b >> 2] >> (8 * (b & 3))) & 255u) >= T) found++;
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) found += __shfl_xor(found, o);
+  return found;
+}
+
+// retainBest(2N) of one (frame, level) by FAST score and, with do_harris, the Harris responses of what it keeps: the
+// candidate list (n entries at cm.x) -> the level's stage-1 list and its count.  The body of k_thr_harris, and of a
+// finish unit of the walker launch (one wave): a workgroup of nt threads, all of them here.
+struct Stage1Smem {
+  uint32_t hist[256];
+  uint32_t thr, lcount;
+};
+template <int RG>
+__device__ __forceinline__ void stage1_from_list(Stage1Smem& S, const OrbGeometry& g, const FrameSrc& src, const uint8_t* pyr,
+                                                 const int l, const int fi, const uint32_t n, const uint2 cm,
+                                                 const uint32_t* cand_key, const uint8_t* cand_sc, uint32_t* s1_cnt,
+                                                 uint4* s1, uint32_t* status, int do_harris, const int tid,
+                                                 const uint32_t nt) {
+  const int slot = src.slot0 + fi;
+  const OrbLevelInfo L = g.lv[l];
+  const uint32_t* keys = cand_key + cm.x;
+  const uint8_t* scs = cand_sc + cm.x;   // 16-byte aligned (every region starts at a multiple of 16 entries)
+  uint4* out = s1 + (long long)slot * g.s1_total + L.s1_off;
+  for (uint32_t b = tid; b < 256u; b += nt) S.hist[b] = 0;
+  if (tid == 0) S.lcount = 0;
+  __syncthreads();
+  // 16 scores per lane and load; bytes past n inside the last group are stale and masked by index
+  for (uint32_t i = 16u * tid; i < n; i += 16u * nt) {
+    const uint4 v = *reinterpret_cast<const uint4*>(scs + i);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int b = 0; b < 16; b++)
+      if (i + b < n) atomicAdd(&S.hist[(w[b >> 2] >> (8 * (b & 3))) & 255u], 1u);
+  }
+  __syncthreads();
+  if (tid < 64) {
+    // KeyPointsFilter::retainBest(keypoints, 2 * featuresNum): keep all >= the (2N)-th largest score = the largest
+    // score b with (number of candidates scoring >= b) >= 2N.  One wave: lane i owns bins 4i .. 4i+3.
+    const uint32_t keep = 2u * (uint32_t)L.quota;
+    const uint32_t h0 = S.hist[4 * tid], h1 = S.hist[4 * tid + 1], h2 = S.hist[4 * tid + 2], h3 = S.hist[4 * tid + 3];
+    uint32_t above = h0 + h1 + h2 + h3;              // -> candidates in the bins of lanes > tid
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t up = __shfl_down(above, o);
+      if (tid + o < 64) above += up;
+    }
+    above -= h0 + h1 + h2 + h3;
+    const uint32_t c3 = above + h3, c2 = c3 + h2, c1 = c2 + h1, c0 = c1 + h0;   // candidates scoring >= 4i+3 .. 4i
+    const int mine = c3 >= keep ? 4 * tid + 3 : c2 >= keep ? 4 * tid + 2 : c1 >= keep ? 4 * tid + 1 : c0 >= keep ? 4 * tid : -1;
+    const unsigned long long ok = __ballot(mine >= 0);
+    uint32_t thr = 0;                                  // n <= 2N: keep everything
+    if (n > keep) {
+      thr = 256;                                       // keep == 0: drop all
+      if (keep > 0 && ok) thr = (uint32_t)__shfl(mine, 63 - __builtin_clzll(ok));
+    }
+    if (tid == 0) S.thr = thr;
+  }
+  __syncthreads();
+  const uint32_t thr = S.thr;
+  int pitch;
+  const uint8_t* img = level_ptr(g, src, pyr, fi, l, &pitch);
+  // pass 1: compact the kept candidates (score >= thr) into the stage-1 list, response pending.  Kept candidates are
+  // a few hundred out of tens of thousands: most waves see none and move on.
+  for (uint32_t i0 = 0; i0 < n; i0 += 16u * nt) {
+    const uint32_t i = i0 + 16u * tid;
+    uint32_t mask = 0;
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (i < n) {
+      v = *reinterpret_cast<const uint4*>(scs + i);
+      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int b = 0; b < 16; b++)
+        if (i + b < n && ((w[b >> 2] >> (8 * (b & 3))) & 255u) >= thr) mask |= 1u << b;
+    }
+    if (__ballot(mask != 0u) == 0ull) continue;
+    uint32_t k = reserve_packed(__popc(mask), &S.lcount, tid & 63);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    while (mask) {
+      const int b = __ffs(mask) - 1;
+      mask &= mask - 1;
+      if (k < (uint32_t)kS1Cap)
+        out[k] = make_uint4(keys[i + b], 0u, (w[b >> 2] >> (8 * (b & 3))) & 255u, 0u);
+      k++;
+    }
+  }
+  __syncthreads();
+  // pass 2: Harris response on dense lanes
+  // (batches whose levels were not finished inside the walker launch leave this pass to k_harris_flat: there the kept
+  // candidates of ALL (frame, level)s are spread evenly over waves of one round each, instead of one wave per
+  // (frame, level) walking up to four dependent rounds)
+  const uint32_t kept = !do_harris ? 0u : min(S.lcount, (uint32_t)kS1Cap);
+  for (uint32_t i = tid; i < kept; i += nt) {
+    const uint32_t key = out[i].x;
+    const float r = harris_at<RG>(img, pitch, key & 0xFFFF, key >> 16);
+    out[i].y = __float_as_uint(r);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    uint32_t m = S.lcount;
+    if (m > (uint32_t)kS1Cap) { atomicOr(&status[slot], kStatusOverflow); m = kS1Cap; }
+    s1_cnt[slot * kOrbLevels + l] = m;
+  }
+}
+
+// The finish unit of (frame fi, level l): one wave of the walker launch that does, while other units keep the vector
+// pipes busy, what k_fast_check, k_thr_harris and k_harris_flat do for the (frame, level) behind the launch.  It waits
+// -- bounded, like every unit -- until every strip of the (frame, level) has counted itself done: the strips' candidate
+// keys and score bytes are then in memory (write-through stores, drained before the count), and so is the level itself
+// (its threshold unit waited for it before any of its strips started).  Then k_fast_check's test: a level that must be
+// redone densely is queued exactly as there and left to the launches behind the walker; every other level gets its
+// stage-1 list with the Harris responses and is marked finished (kQFin), which those launches skip.
+using FinishSmem = Stage1Smem;
+static_assert(sizeof(FinishSmem) <= sizeof(StreamSmem), "the finish unit works in the walker's LDS block");
+__device__ __forceinline__ void finish_unit(FinishSmem& S, const OrbGeometry& g, const FrameSrc& src, const uint8_t* pyr,
+                                            uint32_t* tau, uint32_t* tau_first, uint32_t* qstat, uint32_t* cand_cnt,
+                                            const uint32_t* cand_key, const uint8_t* cand_sc, const uint2* cmap,
+                                            uint32_t* redo_cnt, uint32_t* redo_list, uint32_t* s1_cnt, uint4* s1,
+                                            uint32_t* status, uint32_t* abort_word, const int l, const int fi) {
+  const int lane = threadIdx.x, slot = src.slot0 + fi, idx = slot * kOrbLevels + l;
+  uint32_t* const qs = qstat + (size_t)idx * kQStat;
+  // (every level has at least one strip -- plan_orb: wk_nx >= 1, wk_ny >= 1 for a level of at least one row --, and a
+  // strip counts itself only after it has seen the level's threshold published: once the count is met, kQFirst in the
+  // same poll carries kQReady.  A level without strips would pass this wait before its threshold exists.)
+  const uint32_t n_strips = (uint32_t)(g.lv[l].wk_nx * g.lv[l].wk_ny);
+  uint32_t qx = ld_agent(&qs[kTauBins + (lane & 3)]);
+  bool ready = false;
+  for (uint32_t it = 0; it < kSpinMax; it++) {
+    ready = (uint32_t)__builtin_amdgcn_readlane((int)qx, kQAll - kTauBins) >= n_strips;
+    if (ready || ld_agent(abort_word) != 0u) break;     // uniform
+    __builtin_amdgcn_s_sleep(20);
+    qx = ld_agent(&qs[kTauBins + (lane & 3)]);
+  }
+  if (!ready) {
+    unit_stall(status, slot, abort_word, lane);
+    return;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");       // the lists and the level's pixels are read below
+  const uint32_t first = (uint32_t)__builtin_amdgcn_readlane((int)qx, kQFirst - kTauBins) & ~kQReady;
+  const uint2 cm = cmap[idx];
+  const uint32_t cnt = ld_agent(&cand_cnt[idx]);
+  const uint32_t n = min(cnt, cm.y);
+  if (first <= (uint32_t)kFastT) {
+    // fastThreshold from the start: a level with a key point rectangle was queued for the dense pass by its threshold
+    // unit and is finished behind the launch; one without (it lies inside the 31-px border) has an empty list for good
+    if (g.lv[l].tiles_x > 0) return;
+  } else {
+    // the largest threshold any strip ran at (every strip's atomicMax was performed before it counted itself done)
+    const uint32_t T = max(first, ld_agent(&qs[kQTau]));
+    const uint32_t found = count_scores_from(cand_sc + cm.x, n, T, lane);
+    if (cnt > cm.y || found < 2u * (uint32_t)g.lv[l].quota) {   // as k_fast_check: incomplete list, or too few strong corners
+      if (lane == 0) {
+        st_agent(&tau[idx], (uint32_t)kFastT);
+        st_agent(&cand_cnt[idx], 0u);
+        redo_list[atomicAdd(redo_cnt, 1u)] = (uint32_t)(fi * kOrbLevels + l);
+      }
+      return;
+    }
+    if (lane == 0) {
+      st_agent(&tau[idx], T);                              // the threshold the list is complete from
+      st_agent(&tau_first[idx], T);
+    }
+  }
+  stage1_from_list<3>(S, g, src, pyr, l, fi, n, cm, cand_key, cand_sc, s1_cnt, s1, status, 1, lane, 64u);
+  if (lane == 0) st_agent(&qs[kQFin], 1u);
 }
 
 // The walker launch: see "the one-launch form" above walk_strip.  resize_mask bit l: the strips of level l also make
@@ -1423,39 +1692,24 @@ __global__ __launch_bounds__(64) void k_walk(OrbGeometry g, FrameSrc src, uint8_
                                              uint32_t* redo_cnt, uint32_t* redo_list,
                                              uint32_t* status, uint32_t* abort_word, int l_lo, int l_hi, int n_frames,
                                              int margin_pct, int dyn, int force_tau, int predict_pct, int chain,
-                                             int resize_mask, int test_stall_frame) {
+                                             int resize_mask, int test_stall_frame, int finish, uint32_t* s1_cnt,
+                                             uint4* s1) {
   __shared__ StreamSmem sm;
-  const int xcd = (int)(blockIdx.x & 7u);
-  int r = (int)(blockIdx.x >> 3);                // unit of this XCD
-  const int nf8 = n_frames >> 3, nrem = n_frames & 7;
-  const int nfx = nf8 + (xcd < nrem ? 1 : 0), f0 = xcd * nf8 + (xcd < nrem ? xcd : nrem);
-  int l = l_lo, S = 0;
-  for (;; l++) {
-    if (l > l_hi) return;                        // surplus workgroups of an XCD with one frame fewer
-    S = g.lv[l].wk_nx * g.lv[l].wk_ny;
-    const int units = nfx * (1 + S);
-    if (r < units) break;
-    r -= units;
-  }
-  if (r < nfx) {
+  const WalkUnit u = walk_unit(g, l_lo, l_hi, n_frames, finish, blockIdx.x);   // (orb_plan.h: the unit order)
+  if (u.kind == kWalkNone) return;
+  const int l = u.level, fi = u.frame, ts = u.strip;
+  if (u.kind == kWalkThreshold) {
     // test hook (MSF_TEST_HOOKS=1 + MSF_ORB_TEST_STALL_FRAME=f, never set otherwise): the threshold of (frame f, level 3)
     // is never published, so that the bounded waits, the abort word and the per-frame error flag can be exercised
-    if (f0 + r == test_stall_frame && l == 3) return;
+    if (fi == test_stall_frame && l == 3) return;
     tau_unit(*reinterpret_cast<TauSmem*>(&sm), g, src, pyr, tau, tau_first, redo_cnt, redo_list, qstat, status, abort_word,
-             force_tau, predict_pct, chain, l, f0 + r);
+             force_tau, predict_pct, chain, l, fi);
     return;
   }
-  r -= nfx;
-  const int Sq = (S + 3) >> 2, Sr = S - Sq;
-  int fi, ts;
-  if (r < nfx * Sq) {
-    fi = f0 + r / Sq;
-    ts = 4 * (r % Sq);
-  } else {
-    r -= nfx * Sq;
-    fi = f0 + r / Sr;
-    const int ip = r % Sr;
-    ts = 4 * (ip / 3) + ip % 3 + 1;
+  if (u.kind == kWalkFinish) {
+    finish_unit(*reinterpret_cast<FinishSmem*>(&sm), g, src, pyr, tau, tau_first, qstat, cand_cnt, cand_key, cand_sc, cmap,
+                redo_cnt, redo_list, s1_cnt, s1, status, abort_word, l, fi);
+    return;
   }
   if ((resize_mask >> l) & 1)
     walk_strip<true>(sm, g, src, pyr, tab, qstat, cand_cnt, cand_key, cand_sc, cmap, status, abort_word, margin_pct, dyn, chain, l, fi, ts);
@@ -1473,6 +1727,7 @@ __global__ __launch_bounds__(64) void k_fast_check(OrbGeometry g, int slot0, int
   const int fi = blockIdx.x / kOrbLevels, l = blockIdx.x - fi * kOrbLevels, lane = threadIdx.x;
   if (fi >= n_frames || l >= g.nlevels) return;
   const int idx = (slot0 + fi) * kOrbLevels + l;
+  if (qstat[(size_t)idx * kQStat + kQFin] != 0u) return;                 // checked and finished by its finish unit (k_walk)
   if (tau[idx] <= (uint32_t)kFastT) return;
   const uint32_t T = max(tau[idx], qstat[(size_t)idx * kQStat + kQTau]);   // the largest threshold any strip ran at
   const OrbLevelInfo L = g.lv[l];
@@ -1482,16 +1737,7 @@ __global__ __launch_bounds__(64) void k_fast_check(OrbGeometry g, int slot0, int
   const bool over = cand_cnt[idx] > cm.y;
   const uint32_t n = min(cand_cnt[idx], cm.y);
   const uint8_t* scs = cand_sc + cm.x;
-  uint32_t found = 0;
-  for (uint32_t i = 16u * lane; i < n; i += 16u * 64u) {
-    const uint4 v = *reinterpret_cast<const uint4*>(scs + i);
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int b = 0; b < 16; b++)
-      if (i + b < n && ((w[b >> 2] >> (8 * (b & 3))) & 255u) >= T) found++;
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) found += __shfl_xor(found, o);
+  const uint32_t found = count_scores_from(scs, n, T, lane);
   if (lane == 0) {
     if (over || found < 2u * (uint32_t)L.quota) {
       tau[idx] = kFastT;
@@ -1578,157 +1824,27 @@ __global__ __launch_bounds__(64) void k_redo_thr(OrbGeometry g, int slot0, const
   }
 }
 
-// ------------------------------------------------------------------ K5+K6: retainBest(2N) by FAST score, Harris response
-// HarrisResponses (orb.cpp), blockSize 7, k = 0.04, on the unblurred level.
-// One lane per candidate.  The 9 x 9 neighbourhood comes in as 27 aligned dwords (3 per row; scattered byte loads --
-// ~190 per candidate -- made the texture addresser the bottleneck: 0.67 ms of this stage per 2048 frames), and the
-// Sobel sums are separable dot products on bytes biased by 128 (differences and the 1-2-1 sums of differences are
-// unaffected by the bias):  G[row][j] = p[j+1] - p[j-1],  H[row][j] = p[j-1] + 2 p[j] + p[j+1] - 512,
-//   Ix[r][j] = G[r-1][j] + 2 G[r][j] + G[r+1][j],   Iy[r][j] = H[r+1][j] - H[r-1][j]   (all int32, exact).
-__device__ __forceinline__ float harris_at(const uint8_t* img, int step, int x0, int y0) {
-  const int xb = (x0 - 4) & ~3;
-  const uint32_t o = (uint32_t)(x0 - 4) & 3u;
-  const uint8_t* base = img + (long long)(y0 - 4) * step + xb;
-  constexpr int kWG = 0x000100FF;                                 // weights (-1, 0, +1, 0) on bytes 0..3
-  constexpr int kWH = 0x00010201;                                 // weights ( 1, 2,  1, 0)
-  int Gm2[7], Gm1[7], Hm2[7], Hm1[7];
-  int a = 0, b = 0, c = 0;
-#pragma unroll
-  for (int t = 0; t < 9; t++) {
-    const uint32_t* rp = reinterpret_cast<const uint32_t*>(base + (long long)t * step);
-    const uint32_t d0 = rp[0] ^ 0x80808080u, d1 = rp[1] ^ 0x80808080u, d2 = rp[2] ^ 0x80808080u;
-    const uint32_t w0 = __builtin_amdgcn_alignbyte(d1, d0, o);   // px -4 .. -1 (relative to x0)
-    const uint32_t w1 = __builtin_amdgcn_alignbyte(d2, d1, o);   // px  0 ..  3
-    const uint32_t w2 = d2 >> (8u * o);                          // px  4 in byte 0
-    // windows starting at px j-1 for j = -3 .. 3 (the 4th byte has weight 0)
-    const uint32_t win[7] = {w0, __builtin_amdgcn_alignbyte(w1, w0, 1), __builtin_amdgcn_alignbyte(w1, w0, 2),
-                             __builtin_amdgcn_alignbyte(w1, w0, 3), w1, __builtin_amdgcn_alignbyte(w2, w1, 1),
-                             __builtin_amdgcn_alignbyte(w2, w1, 2)};
-    int G[7], H[7];
-#pragma unroll
-    for (int j = 0; j < 7; j++) {
-      G[j] = __builtin_amdgcn_sdot4((int)win[j], kWG, 0, false);
-      H[j] = __builtin_amdgcn_sdot4((int)win[j], kWH, 0, false);
-    }
-    if (t >= 2) {
-#pragma unroll
-      for (int j = 0; j < 7; j++) {
-        const int Ix = Gm2[j] + 2 * Gm1[j] + G[j];
-        const int Iy = H[j] - Hm2[j];
-        a += Ix * Ix;
-        b += Iy * Iy;
-        c += Ix * Iy;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 7; j++) { Gm2[j] = Gm1[j]; Gm1[j] = G[j]; Hm2[j] = Hm1[j]; Hm1[j] = H[j]; }
-  }
-  const float scale = 1.f / ((1 << 2) * 7 * 255.f);
-  const float scale_sq_sq = scale * scale * scale * scale;
-  const float fa = (float)a, fb = (float)b, fc = (float)c;
-  return (fa * fb - fc * fc - 0.04f * (fa + fb) * (fa + fb)) * scale_sq_sq;
-}
-
+// fin (or null): the walker launch's state; a (frame, level) a finish unit marked there (kQFin) has its stage-1 list and
+// responses already
 __global__ __launch_bounds__(256) void k_thr_harris(OrbGeometry g, FrameSrc src, const uint8_t* pyr,
                                                     const uint32_t* cand_cnt, const uint32_t* cand_key,
                                                     const uint8_t* cand_sc, const uint2* cmap,
-                                                    uint32_t* s1_cnt, uint4* s1, uint32_t* status, int do_harris) {
-  __shared__ uint32_t hist[256];
-  __shared__ uint32_t thr_s, lcount;
+                                                    uint32_t* s1_cnt, uint4* s1, uint32_t* status, int do_harris,
+                                                    const uint32_t* fin) {
+  __shared__ Stage1Smem S;
   // Launched with 256 threads when the candidate lists are the dense ones (tens of thousands per level) and with one
   // wave when they come from the output-sensitive FAST pass (about a thousand): the stage is then a chain of short,
   // latency-bound phases, and four times as many (frame, level)s in flight beat four waves idling at the barriers.
   const int l = blockIdx.x, fi = blockIdx.y, slot = src.slot0 + fi, tid = threadIdx.x;
-  const uint32_t nt = blockDim.x;
   if (l >= g.nlevels) return;
-  const OrbLevelInfo L = g.lv[l];
+  if (fin && fin[(size_t)(slot * kOrbLevels + l) * kQStat + kQFin] != 0u) return;
   uint32_t n = cand_cnt[slot * kOrbLevels + l];
   const uint2 cm = cmap[slot * kOrbLevels + l];
   if (n > cm.y) {
     if (tid == 0) atomicOr(&status[slot], kStatusOverflow);
     n = cm.y;
   }
-  const uint32_t* keys = cand_key + cm.x;
-  const uint8_t* scs = cand_sc + cm.x;   // 16-byte aligned (every region starts at a multiple of 16 entries)
-  uint4* out = s1 + (long long)slot * g.s1_total + L.s1_off;
-  for (uint32_t b = tid; b < 256u; b += nt) hist[b] = 0;
-  if (tid == 0) lcount = 0;
-  __syncthreads();
-  // 16 scores per lane and load; bytes past n inside the last group are stale and masked by index
-  for (uint32_t i = 16u * tid; i < n; i += 16u * nt) {
-    const uint4 v = *reinterpret_cast<const uint4*>(scs + i);
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int b = 0; b < 16; b++)
-      if (i + b < n) atomicAdd(&hist[(w[b >> 2] >> (8 * (b & 3))) & 255u], 1u);
-  }
-  __syncthreads();
-  if (tid < 64) {
-    // KeyPointsFilter::retainBest(keypoints, 2 * featuresNum): keep all >= the (2N)-th largest score = the largest
-    // score b with (number of candidates scoring >= b) >= 2N.  One wave: lane i owns bins 4i .. 4i+3.
-    const uint32_t keep = 2u * (uint32_t)L.quota;
-    const uint32_t h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
-    uint32_t above = h0 + h1 + h2 + h3;              // -> candidates in the bins of lanes > tid
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t up = __shfl_down(above, o);
-      if (tid + o < 64) above += up;
-    }
-    above -= h0 + h1 + h2 + h3;
-    const uint32_t c3 = above + h3, c2 = c3 + h2, c1 = c2 + h1, c0 = c1 + h0;   // candidates scoring >= 4i+3 .. 4i
-    const int mine = c3 >= keep ? 4 * tid + 3 : c2 >= keep ? 4 * tid + 2 : c1 >= keep ? 4 * tid + 1 : c0 >= keep ? 4 * tid : -1;
-    const unsigned long long ok = __ballot(mine >= 0);
-    uint32_t thr = 0;                                  // n <= 2N: keep everything
-    if (n > keep) {
-      thr = 256;                                       // keep == 0: drop all
-      if (keep > 0 && ok) thr = (uint32_t)__shfl(mine, 63 - __builtin_clzll(ok));
-    }
-    if (tid == 0) thr_s = thr;
-  }
-  __syncthreads();
-  const uint32_t thr = thr_s;
-  int pitch;
-  const uint8_t* img = level_ptr(g, src, pyr, fi, l, &pitch);
-  // pass 1: compact the kept candidates (score >= thr) into the stage-1 list, response pending.  Kept candidates are
-  // a few hundred out of tens of thousands: most waves see none and move on.
-  for (uint32_t i0 = 0; i0 < n; i0 += 16u * nt) {
-    const uint32_t i = i0 + 16u * tid;
-    uint32_t mask = 0;
-    uint4 v = make_uint4(0u, 0u, 0u, 0u);
-    if (i < n) {
-      v = *reinterpret_cast<const uint4*>(scs + i);
-      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int b = 0; b < 16; b++)
-        if (i + b < n && ((w[b >> 2] >> (8 * (b & 3))) & 255u) >= thr) mask |= 1u << b;
-    }
-    if (__ballot(mask != 0u) == 0ull) continue;
-    uint32_t k = reserve_packed(__popc(mask), &lcount, tid & 63);
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    while (mask) {
-      const int b = __ffs(mask) - 1;
-      mask &= mask - 1;
-      if (k < (uint32_t)kS1Cap)
-        out[k] = make_uint4(keys[i + b], 0u, (w[b >> 2] >> (8 * (b & 3))) & 255u, 0u);
-      k++;
-    }
-  }
-  __syncthreads();
-  // pass 2: Harris response on dense lanes
-  // (batches leave this pass to k_harris_flat: there the kept candidates of ALL (frame, level)s are spread evenly over
-  // waves of one round each, instead of one wave per (frame, level) walking up to four dependent rounds)
-  const uint32_t kept = !do_harris ? 0u : min(lcount, (uint32_t)kS1Cap);
-  for (uint32_t i = tid; i < kept; i += nt) {
-    const uint32_t key = out[i].x;
-    const float r = harris_at(img, pitch, key & 0xFFFF, key >> 16);
-    out[i].y = __float_as_uint(r);
-  }
-  __syncthreads();
-  if (tid == 0) {
-    uint32_t m = lcount;
-    if (m > (uint32_t)kS1Cap) { atomicOr(&status[slot], kStatusOverflow); m = kS1Cap; }
-    s1_cnt[slot * kOrbLevels + l] = m;
-  }
+  stage1_from_list<9>(S, g, src, pyr, l, fi, n, cm, cand_key, cand_sc, s1_cnt, s1, status, do_harris, tid, blockDim.x);
 }
 
 // HarrisResponses of the stage-1 lists, balanced: the lists of a frame are cut into units of 64 entries, level l getting
@@ -1737,7 +1853,8 @@ __global__ __launch_bounds__(256) void k_thr_harris(OrbGeometry g, FrameSrc src,
 // of its time here -- level 0 alone is four dependent rounds of 27 scattered loads at 4 waves per SIMD -- 0.39 ms of the
 // 0.56 ms selection stage per 2048 720p frames.  (HarrisUnits: orb_plan.h)
 __global__ __launch_bounds__(256) void k_harris_flat(OrbGeometry g, FrameSrc src, const uint8_t* pyr, HarrisUnits hw,
-                                                     const uint32_t* __restrict__ s1_cnt, uint4* s1) {
+                                                     const uint32_t* __restrict__ s1_cnt, uint4* s1,
+                                                     const uint32_t* fin) {
   const int fi = blockIdx.y, slot = src.slot0 + fi, lane = threadIdx.x & 63;
   const int u = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (u >= hw.base[g.nlevels]) return;
@@ -1745,6 +1862,7 @@ __global__ __launch_bounds__(256) void k_harris_flat(OrbGeometry g, FrameSrc src
 #pragma unroll
   for (int i = 1; i < kOrbLevels; i++)
     if (i < g.nlevels && u >= hw.base[i]) l = i;
+  if (fin && fin[(size_t)(slot * kOrbLevels + l) * kQStat + kQFin] != 0u) return;   // scored by its finish unit (k_walk)
   const OrbLevelInfo L = g.lv[l];
   const uint32_t kept = min(s1_cnt[slot * kOrbLevels + l], (uint32_t)kS1Cap);
   uint4* out = s1 + (long long)slot * g.s1_total + L.s1_off;
@@ -2355,6 +2473,13 @@ void OrbPipeline::read_env() {
   // MSF_ORB_WALK_PER_LEVEL=1: the fused walker as one launch per level instead of one launch over all levels (tests
   // compare the two: the in-launch dependency waits are then met the moment a unit starts)
   if (const char* e = getenv("MSF_ORB_WALK_PER_LEVEL")) walk_per_level_ = atoi(e) != 0;
+  // MSF_ORB_WALK_FINISH=0: no finish units in the one-launch walker -- every level's check, retainBest(2N) cut and
+  // Harris responses are left to the launches behind it (tests compare the two; the same library runs both); 1 / 2: where
+  // the finish units of level l stand among the units of level l + 1 (walk_unit, orb_plan.h)
+  if (const char* e = getenv("MSF_ORB_WALK_FINISH")) {
+    const int v = atoi(e);
+    if (v >= kWalkFinishOff && v <= kWalkFinishQuarter) walk_finish_ = v;
+  }
   // MSF_ORB_TAU_PREDICT: percent of the needed corner density the prediction of a level's first threshold from the level
   // above keeps (0 = sample every level)
   if (const char* e = getenv("MSF_ORB_TAU_PREDICT")) {
@@ -2502,17 +2627,17 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
   const int dyn = (fast_two_part_ && force_tau == 0) ? 1 : 0;
   bool fused = fused_ && !dense && g.total_tiles > 0;
   for (int l = 1; l < g.nlevels; l++) fused = fused && g.lv[l].wk_fused != 0;
-  // the units of levels [l_lo, l_hi]: per XCD ceil(n / 8) frames x (1 threshold unit + the level's strips), see k_walk
-  auto launch_walk = [&](int l_lo, int l_hi, int chain, int resize_mask, int predict_pct) {
-    long long per_frame = 0;
-    for (int l = l_lo; l <= l_hi; l++) per_frame += 1 + g.lv[l].wk_nx * g.lv[l].wk_ny;
-    const long long wgs = 8ll * ((n + 7) / 8) * per_frame;
+  // the units of levels [l_lo, l_hi] (walk_unit / walk_grid, orb_plan.h); finish != 0: with finish units
+  auto launch_walk = [&](int l_lo, int l_hi, int chain, int resize_mask, int predict_pct, int finish) {
+    const long long wgs = walk_grid(g, l_lo, l_hi, n, finish);
     hipLaunchKernelGGL(k_walk, dim3((unsigned)wgs), dim3(64), 0, st, g, src, d_pyr_, d_tab_, tau, tau_first, d_qstat_,
                        d_cand_cnt_, d_cand_, d_cand_sc_, d_cmap_, d_redo_, d_redo_ + 1, d_status_, d_walk_abort_, l_lo, l_hi, n,
-                       tau2_margin_pct_, dyn, force_tau, predict_pct, chain, resize_mask, test_stall_frame_);
+                       tau2_margin_pct_, dyn, force_tau, predict_pct, chain, resize_mask, test_stall_frame_, finish,
+                       this->d_s1_cnt_ - back * kOrbLevels, this->d_s1_ - back * g.s1_total);
   };
   last_fused_ = fused;
   last_dense_ = dense;
+  last_finish_ = false;
   if (!dense && g.total_tiles > 0) {
     // the walker's per-(frame, level) state starts from zero: histograms, counters, "threshold published" words
     if ((e = hipMemsetAsync(this->d_qstat_, 0, (size_t)n * kOrbLevels * kQStat * 4, st))) return e;
@@ -2526,9 +2651,12 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
     const int mask = (1 << (g.nlevels - 1)) - 1;          // every level but the last also makes the next one
     const int predict = dyn ? tau_predict_pct_ : 0;
     if (walk_per_level_) {
-      for (int l = 0; l < g.nlevels; l++) launch_walk(l, l, 1, mask, predict);
+      for (int l = 0; l < g.nlevels; l++) launch_walk(l, l, 1, mask, predict, kWalkFinishOff);
     } else {
-      launch_walk(0, g.nlevels - 1, 1, mask, predict);
+      // all levels in one launch: a finish unit per (frame, level) does the level's check, cut and Harris responses
+      // under the other units' arithmetic (finish_unit)
+      launch_walk(0, g.nlevels - 1, 1, mask, predict, walk_finish_);
+      last_finish_ = walk_finish_ != kWalkFinishOff;
     }
     // both words: this launch's abort word and the sticky stall count (read at the start of a later call; the count
     // survives however many calls are enqueued before the host looks)
@@ -2545,7 +2673,7 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
                            d_cand_cnt_, d_cand_, d_cand_sc_, d_cmap_);
       } else {
         // every level exists: FAST-only strips, every level's first threshold from its own sample
-        launch_walk(0, g.nlevels - 1, 0, 0, 0);
+        launch_walk(0, g.nlevels - 1, 0, 0, 0, kWalkFinishOff);
       }
     }
   }
@@ -2567,7 +2695,8 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
                        g.max_level_tiles, d_cand_cnt_, d_cand_, d_cand_sc_, d_cmap_, (uint32_t*)nullptr, d_redo_thr_);
   }
   if (evs) hipEventRecord(evs[2], st);
-  launch_tail(src, n, dense, st, evs);
+  // (the walker state is zeroed per call whenever the call is not dense: without finish units no level is marked)
+  launch_tail(src, n, dense, st, evs, !dense && g.total_tiles > 0 ? d_qstat_ : nullptr);
   return hipGetLastError();
 }
 
@@ -2592,7 +2721,7 @@ void OrbPipeline::launch_resize(const FrameSrc& src, int n, int l, hipStream_t s
                      magic_groups);
 }
 
-void OrbPipeline::launch_tail(const FrameSrc& src, int n, bool dense, hipStream_t st, hipEvent_t* evs) {
+void OrbPipeline::launch_tail(const FrameSrc& src, int n, bool dense, hipStream_t st, hipEvent_t* evs, const uint32_t* fin) {
   const OrbGeometry& g = g_;
   const ptrdiff_t back = (ptrdiff_t)src.slot0;                 // work rows: see extract_range
   uint8_t* const d_pyr_ = this->d_pyr_ - back * g.pyr_bytes;
@@ -2601,11 +2730,11 @@ void OrbPipeline::launch_tail(const FrameSrc& src, int n, bool dense, hipStream_
   uint32_t* const d_s1_cnt_ = this->d_s1_cnt_ - back * kOrbLevels;
   uint4* const d_s1_ = this->d_s1_ - back * g.s1_total;
   hipLaunchKernelGGL(k_thr_harris, dim3(g.nlevels, n), dim3(dense ? 256 : 64), 0, st, g, src, d_pyr_,
-                     d_cand_cnt_, d_cand_, d_cand_sc_, d_cmap_, d_s1_cnt_, d_s1_, d_status_, dense ? 1 : 0);
+                     d_cand_cnt_, d_cand_, d_cand_sc_, d_cmap_, d_s1_cnt_, d_s1_, d_status_, dense ? 1 : 0, fin);
   if (!dense) {
     const HarrisUnits& hw = harris_;
     const int nu = hw.base[kOrbLevels];
-    hipLaunchKernelGGL(k_harris_flat, dim3((nu + 3) / 4, n), dim3(256), 0, st, g, src, d_pyr_, hw, d_s1_cnt_, d_s1_);
+    hipLaunchKernelGGL(k_harris_flat, dim3((nu + 3) / 4, n), dim3(256), 0, st, g, src, d_pyr_, hw, d_s1_cnt_, d_s1_, fin);
   }
   hipLaunchKernelGGL(k_select, dim3(n), dim3(256), 0, st, g, src.slot0, d_s1_cnt_, d_s1_, d_kp_, d_kp_cnt_,
                      d_status_);
@@ -2672,7 +2801,7 @@ hipError_t OrbPipeline::tail(const FrameSrc& src, int n, const int32_t* counts, 
   }
   if (!e) e = hipMemcpyAsync(this->d_cand_cnt_, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice, st);
   if (!e) {
-    launch_tail(src, n, form == 0, st, nullptr);
+    launch_tail(src, n, form == 0, st, nullptr, nullptr);   // the caller's lists: no level was finished by a walker
     e = hipGetLastError();
   }
   const hipError_t es = hipStreamSynchronize(st);     // the copies read this call's host arrays
@@ -2897,6 +3026,20 @@ int OrbPipeline::debug_get(int what, int slot, int level, void* host_out, size_t
       for (int l = 0; l < kOrbLevels; l++) { v[l][0] = (int32_t)t[0][l]; v[l][1] = (int32_t)t[1][l]; }
       *n_bytes = sizeof(v);
       memcpy(host_out, v, sizeof(v) < cap ? sizeof(v) : cap);
+      return 0;
+    }
+    case MSF_DBG_WALK_FINISHED: {
+      // bit l: level l of the slot was finished by its finish unit inside the last extraction's walker launch
+      int32_t mask = 0;
+      if (last_finish_) {
+        for (int l = 0; l < g.nlevels; l++) {
+          uint32_t f = 0;
+          hipMemcpy(&f, d_qstat_ + ((size_t)row * kOrbLevels + l) * kQStat + kQFin, 4, hipMemcpyDeviceToHost);
+          if (f) mask |= 1 << l;
+        }
+      }
+      *n_bytes = sizeof(mask);
+      memcpy(host_out, &mask, sizeof(mask) < cap ? sizeof(mask) : cap);
       return 0;
     }
     case MSF_DBG_STAGE1: {

@@ -103,6 +103,9 @@ class OrbPipeline {
   bool fused_ = true;                     // MSF_ORB_UNFUSED=1 clears it: k_resize x 7, then one FAST-only walker launch
   bool walk_per_level_ = false;           // MSF_ORB_WALK_PER_LEVEL=1: the fused walker as one launch per level (the
                                           // in-launch waits are then met at once); tests compare it with the one-launch default
+  int walk_finish_ = kWalkFinishThr;      // MSF_ORB_WALK_FINISH: finish units inside the one-launch walker (0 off, 1 behind
+                                          // the next level's threshold units, 2 behind its sampled quarter; orb_plan.h)
+  bool last_finish_ = false;              // the last extraction's walker launch held finish units (MSF_DBG_WALK_FINISHED)
   int test_stall_frame_ = -1;             // MSF_TEST_HOOKS + MSF_ORB_TEST_STALL_FRAME: see k_walk
   int tau2_margin_pct_ = 200;             // MSF_ORB_TAU2_MARGIN_PCT
   bool resize_generic_ = false;           // MSF_ORB_RESIZE_GENERIC: never
@@ -152,7 +155,9 @@ class OrbPipeline {
   void launch_resize(const FrameSrc& src, int n, int l, hipStream_t st);
   // selection and description of n frames whose candidate lists are complete: k_thr_harris (dense_form: 256 threads,
   // scoring what it keeps; else one wave + k_harris_flat), k_select, k_describe; evs as extract_range (3 and 4 recorded)
-  void launch_tail(const FrameSrc& src, int n, bool dense_form, hipStream_t st, hipEvent_t* evs);
+  // fin: the walker state of this call (its kQFin words name the (frame, level)s already finished inside the walker
+  // launch, which the selection kernels skip), or null
+  void launch_tail(const FrameSrc& src, int n, bool dense_form, hipStream_t st, hipEvent_t* evs, const uint32_t* fin);
 };
 
 }  // namespace msf

@@ -105,6 +105,62 @@ struct HarrisUnits {
   int n[kOrbLevels];
 };
 
+// ---- the unit order of a walker launch (k_walk): which unit workgroup wg is.  The kernel and the host's grid size both
+// come from here; tests/cpp/walk_units_main.cpp holds the order to what the kernel's waits rest on (every unit exactly
+// once, every dependency at a lower workgroup index).
+// A launch covers levels [l_lo, l_hi] of n_frames frames.  Workgroups b, b + 8, ... share an XCD (observed placement,
+// speed only): XCD x takes the frames [x n / 8, (x + 1) n / 8) and walks, level by level, the THRESHOLD units of its
+// frames, the sampled quarter of all their strips (strip index a multiple of 4), then the other strips.  With finish
+// units (finish = kWalkFinishThr / kWalkFinishQuarter) the FINISH units of level l - 1 stand directly behind the
+// threshold units / behind the sampled quarter of level l -- both wait for all strips of level l - 1 -- and those of
+// level l_hi behind its last strips.  An XCD with one frame fewer than another leaves its surplus workgroups without a unit.
+#if defined(__HIPCC__)
+#define MSF_PLAN_HD __host__ __device__
+#else
+#define MSF_PLAN_HD
+#endif
+constexpr int kWalkNone = 0, kWalkThreshold = 1, kWalkStrip = 2, kWalkFinish = 3;
+constexpr int kWalkFinishOff = 0, kWalkFinishThr = 1, kWalkFinishQuarter = 2;
+struct WalkUnit {
+  int kind, level, frame, strip;   // frame: index inside the call; strip: kWalkStrip only
+};
+MSF_PLAN_HD inline WalkUnit walk_unit(const OrbGeometry& g, int l_lo, int l_hi, int n_frames, int finish, unsigned wg) {
+  const int xcd = (int)(wg & 7u);
+  int r = (int)(wg >> 3);                        // unit of this XCD
+  const int nf8 = n_frames >> 3, nrem = n_frames & 7;
+  const int nfx = nf8 + (xcd < nrem ? 1 : 0), f0 = xcd * nf8 + (xcd < nrem ? xcd : nrem);
+  for (int l = l_lo; l <= l_hi; l++) {
+    const int S = g.lv[l].wk_nx * g.lv[l].wk_ny;
+    if (r < nfx) return WalkUnit{kWalkThreshold, l, f0 + r, 0};
+    r -= nfx;
+    if (finish == kWalkFinishThr && l > l_lo) {
+      if (r < nfx) return WalkUnit{kWalkFinish, l - 1, f0 + r, 0};
+      r -= nfx;
+    }
+    const int Sq = (S + 3) >> 2, Sr = S - Sq;
+    if (r < nfx * Sq) return WalkUnit{kWalkStrip, l, f0 + r / Sq, 4 * (r % Sq)};
+    r -= nfx * Sq;
+    if (finish == kWalkFinishQuarter && l > l_lo) {
+      if (r < nfx) return WalkUnit{kWalkFinish, l - 1, f0 + r, 0};
+      r -= nfx;
+    }
+    if (r < nfx * Sr) {
+      const int ip = r % Sr;
+      return WalkUnit{kWalkStrip, l, f0 + r / Sr, 4 * (ip / 3) + ip % 3 + 1};
+    }
+    r -= nfx * Sr;
+  }
+  if (finish != kWalkFinishOff && r < nfx) return WalkUnit{kWalkFinish, l_hi, f0 + r, 0};
+  return WalkUnit{kWalkNone, 0, 0, 0};           // surplus workgroups of an XCD with one frame fewer
+}
+// workgroups of the launch: per XCD ceil(n / 8) frames x (per level one threshold unit + the level's strips [+ one
+// finish unit])
+inline long long walk_grid(const OrbGeometry& g, int l_lo, int l_hi, int n_frames, int finish) {
+  long long per_frame = 0;
+  for (int l = l_lo; l <= l_hi; l++) per_frame += 1 + g.lv[l].wk_nx * g.lv[l].wk_ny + (finish != kWalkFinishOff ? 1 : 0);
+  return 8ll * ((n_frames + 7) / 8) * per_frame;
+}
+
 struct OrbPlanRequest {
   int width = 0, height = 0;
   int max_slots = 0;

@@ -900,6 +900,11 @@ class FeatureMatcher(_Matcher):
         v = self._debug(_lib.DBG_WALK_MODE, 0, 0, np.int32, 8)
         return bool(v[0]), int(v[1])
 
+    def walk_finished(self, slot, cache=False):
+        """bit mask of the levels of `slot` that were finished -- completeness check, retainBest(2N) cut, Harris responses
+        -- by a finish unit inside the last extraction's walker launch (MSF_DBG_WALK_FINISHED)"""
+        return int(self._debug(_lib.DBG_WALK_FINISHED, self._slot(slot, cache), 0, np.int32, 4)[0])
+
     def walker_launches(self, stage):
         """Launches of the dominant kernel (the streaming walker k_walk) in one extraction of a batch: ONE -- all levels,
         their thresholds and the pyramid in one launch (r03: 2 chains x 8 levels of sampler + walker launches); eight when
