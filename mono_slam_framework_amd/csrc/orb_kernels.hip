@@ -51,7 +51,7 @@ __device__ __forceinline__ const uint8_t* level_ptr(const OrbGeometry& g, const 
                         : src.b + (long long)(fi - src.n_a) * src.frame_stride;
   }
   *pitch = g.lv[l].pitch;
-  return pyr + (long long)(src.slot0 + fi) * g.pyr_bytes + g.lv[l].pix_off;
+  return pyr + (long long)fi * g.pyr_bytes + g.lv[l].pix_off;   // the pyramid is per call: row fi
 }
 
 typedef unsigned short us2_t __attribute__((ext_vector_type(2)));
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void k_resize(OrbGeometry g, FrameSrc src, uin
   const int sh = g.lv[l - 1].h, sw16 = (g.lv[l - 1].w + 16 + 15) & ~15;   // staged row: source width + 16 zero/pad bytes
   int spitch;
   const uint8_t* s = level_ptr(g, src, pyr, fi, l - 1, &spitch);
-  uint8_t* d = pyr + (long long)(src.slot0 + fi) * g.pyr_bytes + L.pix_off;
+  uint8_t* d = pyr + (long long)fi * g.pyr_bytes + L.pix_off;
   const int groups = (L.w + 3) >> 2;
   const uint4* xsel = reinterpret_cast<const uint4*>(tab + L.tab_off);   // [groups] selectors, weight pairs, pair offsets
   const uint4* xwxp = xsel + groups;
@@ -287,7 +287,7 @@ struct FastSmem {
   uint32_t nbd, lcount, gbase;   // nbd: brighter count (low 16) | darker count (high 16)
 };
 
-// ---- where the candidate list of (frame, level) lives: cmap[slot * 8 + level] = (first entry, capacity) in the
+// ---- where the candidate list of (frame, level) lives: cmap[fi * 8 + level] = (first entry, capacity) in the
 // candidate arrays -- the level's primary list inside the frame's work row, or (a dense call) the level's full-capacity
 // list inside the frame's region of the pool (orb_pipeline.h)
 __global__ __launch_bounds__(256) void k_cand_reset(OrbGeometry g, OrbPrimLists prim, uint2* cmap_rows, int n_frames,
@@ -317,7 +317,7 @@ __device__ __forceinline__ void fast_tile(const OrbGeometry& g, const FrameSrc& 
   uint8_t* sc = S_.sc;
   uint16_t* list1 = S_.list1;
   uint2* llist = S_.llist;
-  const int slot = src.slot0 + fi;
+  const int idx = fi * kOrbLevels + l;   // per-call arrays: by frame of the call
   const OrbLevelInfo L = g.lv[l];
   const int x0 = kTileX0 + (t % L.tiles_x) * TW, y0 = kTileY0 + (t / L.tiles_x) * TH;
   int pitch;
@@ -466,14 +466,14 @@ __device__ __forceinline__ void fast_tile(const OrbGeometry& g, const FrameSrc& 
     __syncthreads();
     const uint32_t n = S_.lcount;
     if (hist) {     // uniform: count, do not list
-      uint32_t* const hl = hist + (size_t)(slot * kOrbLevels + l) * 256u;
+      uint32_t* const hl = hist + (size_t)idx * 256u;
       for (uint32_t i = tid; i < n; i += kFastThreads) atomicAdd(&hl[llist[i].y], 1u);
     } else if (n != 0) {   // uniform
-      if (tid == 0) S_.gbase = atomicAdd(&cand_cnt[slot * kOrbLevels + l], n);
+      if (tid == 0) S_.gbase = atomicAdd(&cand_cnt[idx], n);
       __syncthreads();
       const uint32_t base = S_.gbase;
       // structure of arrays: the retainBest threshold pass reads every score (1 byte) but only a few hundred keys
-      const uint2 cm = cmap[slot * kOrbLevels + l];
+      const uint2 cm = cmap[idx];
       uint32_t* outk = cand_key + cm.x;
       uint8_t* outs = cand_sc + cm.x;
       for (uint32_t i = tid; i < n; i += kFastThreads)
@@ -655,7 +655,7 @@ __device__ __forceinline__ void walk_strip(StreamSmem& sm, const OrbGeometry& g,
   const int lane = threadIdx.x;
   const bool quarter = (ts & 3) == 0;
   const OrbLevelInfo L = g.lv[l];
-  const int slot = src.slot0 + fi, idx = slot * kOrbLevels + l;
+  const int idx = fi * kOrbLevels + l;      // per-call arrays: by frame of the call (status alone is per slot: slot0 + fi)
   const int sy = ts / L.wk_nx, sx = ts - sy * L.wk_nx;
   uint32_t* const qs = qstat + (size_t)idx * kQStat;
   const int n_strips = L.wk_nx * L.wk_ny;
@@ -715,7 +715,7 @@ __device__ __forceinline__ void walk_strip(StreamSmem& sm, const OrbGeometry& g,
       qx = ld_agent(&qs[kTauBins + (lane & 3)]);
     }
     if (!ready) {
-      unit_stall(status, slot, abort_word, lane);
+      unit_stall(status, src.slot0 + fi, abort_word, lane);   // status is per slot
       return;
     }
   }
@@ -803,7 +803,7 @@ __device__ __forceinline__ void walk_strip(StreamSmem& sm, const OrbGeometry& g,
     roff0 = rz_lane ? qov.x - (uint32_t)xs : 0u;
     roff3 = rz_lane ? qov.w - (uint32_t)xs : 0u;
     dpitch = uniform_u32((uint32_t)Ld.pitch);
-    dst_rs = uniform_rsrc(pyr + (long long)slot * g.pyr_bytes + Ld.pix_off, (uint32_t)Ld.h * (uint32_t)Ld.pitch);
+    dst_rs = uniform_rsrc(pyr + (long long)fi * g.pyr_bytes + Ld.pix_off, (uint32_t)Ld.h * (uint32_t)Ld.pitch);
     dxoff = rz_lane ? 4u * (uint32_t)gq : kRzNoStore;
     // emit entries of the source rows R0 - 4 + j, j = 64 k + lane in em<k>: output row | w1 << 16 | 1 << 31
     // if an output row has source rows (y, y + 1) as its taps and y is owned by this strip
@@ -1271,7 +1271,8 @@ __device__ __forceinline__ void tau_unit(TauSmem& T, const OrbGeometry& g, const
                                          uint32_t* tau, uint32_t* tau_first, uint32_t* redo_cnt, uint32_t* redo_list,
                                          uint32_t* qstat, uint32_t* status, uint32_t* abort_word, int force_tau,
                                          int predict_pct, int chain, const int l, const int fi) {
-  const int lane = threadIdx.x, slot = src.slot0 + fi, idx = slot * kOrbLevels + l;
+  const int lane = threadIdx.x;
+  const int idx = fi * kOrbLevels + l;      // per-call arrays: by frame of the call (status alone is per slot: slot0 + fi)
   const OrbLevelInfo L = g.lv[l];
   uint32_t* const qs = qstat + (size_t)idx * kQStat;
   int tv = kFastT, pre_used = kTauPre, predicted = 0;
@@ -1291,7 +1292,7 @@ __device__ __forceinline__ void tau_unit(TauSmem& T, const OrbGeometry& g, const
       px = ld_agent(&pq[kTauBins + (lane & 3)]);
     }
     if (!ready) {
-      unit_stall(status, slot, abort_word, lane);
+      unit_stall(status, src.slot0 + fi, abort_word, lane);   // status is per slot
       return;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");     // the sampler below reads level l's pixels
@@ -1536,11 +1537,10 @@ __device__ __forceinline__ void stage1_from_list(Stage1Smem& S, const OrbGeometr
                                                  const uint32_t* cand_key, const uint8_t* cand_sc, uint32_t* s1_cnt,
                                                  uint4* s1, uint32_t* status, int do_harris, const int tid,
                                                  const uint32_t nt) {
-  const int slot = src.slot0 + fi;
   const OrbLevelInfo L = g.lv[l];
   const uint32_t* keys = cand_key + cm.x;
   const uint8_t* scs = cand_sc + cm.x;   // 16-byte aligned (every region starts at a multiple of 16 entries)
-  uint4* out = s1 + (long long)slot * g.s1_total + L.s1_off;
+  uint4* out = s1 + (long long)fi * g.s1_total + L.s1_off;   // s1 and s1_cnt are per call: row fi
   for (uint32_t b = tid; b < 256u; b += nt) S.hist[b] = 0;
   if (tid == 0) S.lcount = 0;
   __syncthreads();
@@ -1617,8 +1617,8 @@ __device__ __forceinline__ void stage1_from_list(Stage1Smem& S, const OrbGeometr
   __syncthreads();
   if (tid == 0) {
     uint32_t m = S.lcount;
-    if (m > (uint32_t)kS1Cap) { atomicOr(&status[slot], kStatusOverflow); m = kS1Cap; }
-    s1_cnt[slot * kOrbLevels + l] = m;
+    if (m > (uint32_t)kS1Cap) { atomicOr(&status[src.slot0 + fi], kStatusOverflow); m = kS1Cap; }   // status is per slot
+    s1_cnt[fi * kOrbLevels + l] = m;
   }
 }
 
@@ -1636,7 +1636,8 @@ __device__ __forceinline__ void finish_unit(FinishSmem& S, const OrbGeometry& g,
                                             const uint32_t* cand_key, const uint8_t* cand_sc, const uint2* cmap,
                                             uint32_t* redo_cnt, uint32_t* redo_list, uint32_t* s1_cnt, uint4* s1,
                                             uint32_t* status, uint32_t* abort_word, const int l, const int fi) {
-  const int lane = threadIdx.x, slot = src.slot0 + fi, idx = slot * kOrbLevels + l;
+  const int lane = threadIdx.x;
+  const int idx = fi * kOrbLevels + l;      // per-call arrays: by frame of the call (status alone is per slot: slot0 + fi)
   uint32_t* const qs = qstat + (size_t)idx * kQStat;
   // (every level has at least one strip -- plan_orb: wk_nx >= 1, wk_ny >= 1 for a level of at least one row --, and a
   // strip counts itself only after it has seen the level's threshold published: once the count is met, kQFirst in the
@@ -1651,7 +1652,7 @@ __device__ __forceinline__ void finish_unit(FinishSmem& S, const OrbGeometry& g,
     qx = ld_agent(&qs[kTauBins + (lane & 3)]);
   }
   if (!ready) {
-    unit_stall(status, slot, abort_word, lane);
+    unit_stall(status, src.slot0 + fi, abort_word, lane);   // status is per slot
     return;
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");       // the lists and the level's pixels are read below
@@ -1721,13 +1722,13 @@ __global__ __launch_bounds__(64) void k_walk(OrbGeometry g, FrameSrc src, uint8_
 // with a score at or above it is in the candidate list (strips that ran lower also left smaller ones).  If fewer than 2N
 // reach it, retainBest(2N) would cut below what was searched completely: the level is queued for the dense pass (its
 // candidate list restarts from empty).  So is a level whose list overflowed its primary list.  One wave per (frame, level).
-__global__ __launch_bounds__(64) void k_fast_check(OrbGeometry g, int slot0, int n_frames, uint32_t* tau, uint32_t* tau_first,
+__global__ __launch_bounds__(64) void k_fast_check(OrbGeometry g, int n_frames, uint32_t* tau, uint32_t* tau_first,
                                                    uint32_t* cand_cnt, const uint8_t* cand_sc, const uint2* cmap,
                                                    uint32_t* redo_cnt, uint32_t* redo_list, const uint32_t* qstat) {
   const int fi = blockIdx.x / kOrbLevels, l = blockIdx.x - fi * kOrbLevels, lane = threadIdx.x;
   if (fi >= n_frames || l >= g.nlevels) return;
-  const int idx = (slot0 + fi) * kOrbLevels + l;
-  if (qstat[(size_t)idx * kQStat + kQFin] != 0u) return;                 // checked and finished by its finish unit (k_walk)
+  const int idx = fi * kOrbLevels + l;     // per-call arrays only: by frame of the call
+  if (qstat[(size_t)idx * kQStat + kQFin] != 0u) return;                // checked and finished by its finish unit (k_walk)
   if (tau[idx] <= (uint32_t)kFastT) return;
   const uint32_t T = max(tau[idx], qstat[(size_t)idx * kQStat + kQTau]);   // the largest threshold any strip ran at
   const OrbLevelInfo L = g.lv[l];
@@ -1777,7 +1778,7 @@ __global__ __launch_bounds__(kFastThreads) void k_fast_redo(OrbGeometry g, Frame
     if (t >= g.lv[l].tiles_x * g.lv[l].tiles_y) continue;   // uniform
     uint32_t emit_min = 0u;
     if (emit_thr) {
-      emit_min = emit_thr[(src.slot0 + fi) * kOrbLevels + l];
+      emit_min = emit_thr[item];                             // per call: item = fi * kOrbLevels + l
       if (emit_min > 255u) continue;                         // uniform: retainBest(0) keeps nothing
     }
     fast_tile(g, src, pyr, fi, l, t, kFastT, cand_cnt, cand_key, cand_sc, cmap, sm, hist, emit_min);
@@ -1791,15 +1792,15 @@ __global__ __launch_bounds__(kFastThreads) void k_fast_redo(OrbGeometry g, Frame
 // scoring >= b) >= 2N (ties kept); 256 (list none) when 2N = 0 -- as k_thr_harris computes it from a list, which then
 // finds the same cut again.  Leaves the histogram zeroed for the next call (it is zeroed once at init; only the first
 // dense launch adds to it).  One wave per queue entry, a fixed grid walking the queue.
-__global__ __launch_bounds__(64) void k_redo_thr(OrbGeometry g, int slot0, const uint32_t* __restrict__ redo_cnt,
+__global__ __launch_bounds__(64) void k_redo_thr(OrbGeometry g, const uint32_t* __restrict__ redo_cnt,
                                                  const uint32_t* __restrict__ redo_list, const uint2* cmap, uint32_t* hist,
                                                  uint32_t* emit_thr) {
   const uint32_t n = *redo_cnt;
   const int lane = threadIdx.x;
   for (uint32_t q = blockIdx.x; q < n; q += gridDim.x) {
     const uint32_t item = redo_list[q];
-    const int fi = (int)(item / kOrbLevels), l = (int)(item % kOrbLevels);
-    const int idx = (slot0 + fi) * kOrbLevels + l;
+    const int l = (int)(item % kOrbLevels);
+    const int idx = (int)item;                               // fi * kOrbLevels + l: per-call arrays only
     uint4* const hl = reinterpret_cast<uint4*>(hist + (size_t)idx * 256u);
     const uint4 hv = hl[lane];                               // lane i owns bins 4i .. 4i+3
     hl[lane] = make_uint4(0u, 0u, 0u, 0u);
@@ -1835,11 +1836,13 @@ __global__ __launch_bounds__(256) void k_thr_harris(OrbGeometry g, FrameSrc src,
   // Launched with 256 threads when the candidate lists are the dense ones (tens of thousands per level) and with one
   // wave when they come from the output-sensitive FAST pass (about a thousand): the stage is then a chain of short,
   // latency-bound phases, and four times as many (frame, level)s in flight beat four waves idling at the barriers.
-  const int l = blockIdx.x, fi = blockIdx.y, slot = src.slot0 + fi, tid = threadIdx.x;
+  const int l = blockIdx.x, fi = blockIdx.y, tid = threadIdx.x;
   if (l >= g.nlevels) return;
-  if (fin && fin[(size_t)(slot * kOrbLevels + l) * kQStat + kQFin] != 0u) return;
-  uint32_t n = cand_cnt[slot * kOrbLevels + l];
-  const uint2 cm = cmap[slot * kOrbLevels + l];
+  const int idx = fi * kOrbLevels + l;      // per-call arrays: by frame of the call
+  const int slot = src.slot0 + fi;          // per-slot arrays (here only status)
+  if (fin && fin[(size_t)idx * kQStat + kQFin] != 0u) return;
+  uint32_t n = cand_cnt[idx];
+  const uint2 cm = cmap[idx];
   if (n > cm.y) {
     if (tid == 0) atomicOr(&status[slot], kStatusOverflow);
     n = cm.y;
@@ -1855,17 +1858,17 @@ __global__ __launch_bounds__(256) void k_thr_harris(OrbGeometry g, FrameSrc src,
 __global__ __launch_bounds__(256) void k_harris_flat(OrbGeometry g, FrameSrc src, const uint8_t* pyr, HarrisUnits hw,
                                                      const uint32_t* __restrict__ s1_cnt, uint4* s1,
                                                      const uint32_t* fin) {
-  const int fi = blockIdx.y, slot = src.slot0 + fi, lane = threadIdx.x & 63;
+  const int fi = blockIdx.y, lane = threadIdx.x & 63;      // per-call arrays only: everything by frame of the call
   const int u = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (u >= hw.base[g.nlevels]) return;
   int l = 0;
 #pragma unroll
   for (int i = 1; i < kOrbLevels; i++)
     if (i < g.nlevels && u >= hw.base[i]) l = i;
-  if (fin && fin[(size_t)(slot * kOrbLevels + l) * kQStat + kQFin] != 0u) return;   // scored by its finish unit (k_walk)
+  if (fin && fin[(size_t)(fi * kOrbLevels + l) * kQStat + kQFin] != 0u) return;   // scored by its finish unit (k_walk)
   const OrbLevelInfo L = g.lv[l];
-  const uint32_t kept = min(s1_cnt[slot * kOrbLevels + l], (uint32_t)kS1Cap);
-  uint4* out = s1 + (long long)slot * g.s1_total + L.s1_off;
+  const uint32_t kept = min(s1_cnt[fi * kOrbLevels + l], (uint32_t)kS1Cap);
+  uint4* out = s1 + (long long)fi * g.s1_total + L.s1_off;
   int pitch;
   const uint8_t* img = level_ptr(g, src, pyr, fi, l, &pitch);
   const uint32_t step = 64u * (uint32_t)hw.n[l];
@@ -1887,14 +1890,15 @@ __global__ __launch_bounds__(256) void k_select(OrbGeometry g, int slot0, const 
   __shared__ __attribute__((aligned(16))) float resp[kRespCap];
   __shared__ __attribute__((aligned(16))) uint32_t keys[kSelCap];
   __shared__ uint32_t nkept;
-  const int slot = slot0 + blockIdx.x, tid = threadIdx.x;
+  const int fi = blockIdx.x, tid = threadIdx.x;   // s1 / s1_cnt are per call: by frame of the call
+  const int slot = slot0 + fi;                    // kp, kp_cnt and status are per slot
   msf_keypoint* out = kp + (long long)slot * kKpCap;
   uint32_t base = 0;
   bool overflow = false;
   for (int l = 0; l < g.nlevels; l++) {
     const OrbLevelInfo L = g.lv[l];
-    const uint32_t n = s1_cnt[slot * kOrbLevels + l];
-    const uint4* in = s1 + (long long)slot * g.s1_total + L.s1_off;
+    const uint32_t n = s1_cnt[fi * kOrbLevels + l];
+    const uint4* in = s1 + (long long)fi * g.s1_total + L.s1_off;
     const uint32_t keep = (uint32_t)L.quota;
     if (tid == 0) nkept = 0;
     const bool staged = n > keep && n <= (uint32_t)kRespCap;
@@ -2052,7 +2056,7 @@ __global__ __launch_bounds__(256) void k_describe(OrbGeometry g, FrameSrc src, c
     part = fi & 7;
     fi = (fi & ~7) | (int)blockIdx.x;
   }
-  const int slot = src.slot0 + fi;
+  const int slot = src.slot0 + fi;   // kp, kp_cnt, desc: per slot (the pyramid is per call: level_ptr takes fi)
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;   // (scalar: key-point indices and record addresses are then scalar too)
   for (int i = threadIdx.x; i < 2 * kDiscTasks; i += 256) disc_s[i] = c_disc[i];
   pat_s[threadIdx.x] = reinterpret_cast<const int*>(c_pattern)[threadIdx.x];
@@ -2600,21 +2604,14 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
   const OrbGeometry& g = g_;
   hipError_t e;
   // Work rows: frame i of this call uses row i of the per-call arrays (pyramid, candidate and stage-1 lists, thresholds,
-  // walker state), whatever feature slot its key points go to.  The kernels index everything by slot = slot0 + i, so the
-  // per-call arrays are passed as bases moved back by slot0 rows (never dereferenced below row 0: slots start at slot0).
-  const ptrdiff_t back = (ptrdiff_t)src.slot0;
-  uint8_t* const d_pyr_ = this->d_pyr_ - back * g.pyr_bytes;
-  uint32_t* const d_cand_cnt_ = this->d_cand_cnt_ - back * kOrbLevels;
-  uint2* const d_cmap_ = this->d_cmap_ - back * kOrbLevels;     // (its entries are absolute offsets into d_cand_ / d_cand_sc_)
-  uint32_t* const d_qstat_ = this->d_qstat_ - back * kOrbLevels * kQStat;
-  uint32_t* const d_redo_hist_ = this->d_redo_hist_ - back * kOrbLevels * 256;
-  uint32_t* const d_redo_thr_ = this->d_redo_thr_ - back * kOrbLevels;
-  if ((e = hipMemsetAsync(this->d_cand_cnt_, 0, (size_t)n * kOrbLevels * 4, st))) return e;
+  // walker state), whatever feature slot its key points go to.  The kernels index those arrays by the frame of the call
+  // and only the per-slot arrays (key points, descriptors, their count, the status word) by slot = src.slot0 + i.
+  if ((e = hipMemsetAsync(d_cand_cnt_, 0, (size_t)n * kOrbLevels * 4, st))) return e;
   if ((e = hipMemsetAsync(d_status_ + src.slot0, 0, (size_t)n * 4, st))) return e;
   if ((e = hipMemsetAsync(d_redo_, 0, 4, st))) return e;
   if (evs) hipEventRecord(evs[0], st);
-  uint32_t* tau = d_tau_ - back * kOrbLevels;
-  uint32_t* tau_first = d_tau_ + (ptrdiff_t)work_frames_ * kOrbLevels - back * kOrbLevels;
+  uint32_t* const tau = d_tau_;
+  uint32_t* const tau_first = d_tau_ + (size_t)work_frames_ * kOrbLevels;
   // A call of a few frames (the single-pair MatchFrames, a key frame upload) is latency-bound: a wave of the
   // streaming pass walks its strip in ~90 dependent steps, whereas the dense tile kernel is one short workgroup per
   // tile.  Such calls take k_resize + the dense kernel directly; the result is the same either way.
@@ -2623,7 +2620,7 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
   // where each (frame, level)'s candidate list lives in this call (k_cand_reset): its primary list, or -- a dense call --
   // the frame's full-capacity region in the pool
   if (dense && (long long)n * g.cand_total > (long long)g.pool_entries) return hipErrorInvalidValue;   // (cannot happen: see init)
-  hipLaunchKernelGGL(k_cand_reset, dim3((n * kOrbLevels + 255) / 256), dim3(256), 0, st, g, prim_, this->d_cmap_, n, dense ? 1 : 0);
+  hipLaunchKernelGGL(k_cand_reset, dim3((n * kOrbLevels + 255) / 256), dim3(256), 0, st, g, prim_, d_cmap_, n, dense ? 1 : 0);
   const int dyn = (fast_two_part_ && force_tau == 0) ? 1 : 0;
   bool fused = fused_ && !dense && g.total_tiles > 0;
   for (int l = 1; l < g.nlevels; l++) fused = fused && g.lv[l].wk_fused != 0;
@@ -2633,14 +2630,14 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
     hipLaunchKernelGGL(k_walk, dim3((unsigned)wgs), dim3(64), 0, st, g, src, d_pyr_, d_tab_, tau, tau_first, d_qstat_,
                        d_cand_cnt_, d_cand_, d_cand_sc_, d_cmap_, d_redo_, d_redo_ + 1, d_status_, d_walk_abort_, l_lo, l_hi, n,
                        tau2_margin_pct_, dyn, force_tau, predict_pct, chain, resize_mask, test_stall_frame_, finish,
-                       this->d_s1_cnt_ - back * kOrbLevels, this->d_s1_ - back * g.s1_total);
+                       d_s1_cnt_, d_s1_);
   };
   last_fused_ = fused;
   last_dense_ = dense;
   last_finish_ = false;
   if (!dense && g.total_tiles > 0) {
     // the walker's per-(frame, level) state starts from zero: histograms, counters, "threshold published" words
-    if ((e = hipMemsetAsync(this->d_qstat_, 0, (size_t)n * kOrbLevels * kQStat * 4, st))) return e;
+    if ((e = hipMemsetAsync(d_qstat_, 0, (size_t)n * kOrbLevels * kQStat * 4, st))) return e;
     if ((e = hipMemsetAsync(d_walk_abort_, 0, 4, st))) return e;      // word 0 only: word 1 is the sticky stall count
   }
   if (fused) {
@@ -2667,8 +2664,8 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
     if (evs) hipEventRecord(evs[1], st);
     if (g.total_tiles > 0) {
       if (dense) {   // MSF_FLAG_FAST_DENSE / a call of a few frames: the plain detector over every tile, nothing to verify
-        hipLaunchKernelGGL(k_fill_u32, dim3((n * kOrbLevels + 255) / 256), dim3(256), 0, st, tau + (size_t)src.slot0 * kOrbLevels,
-                           tau_first + (size_t)src.slot0 * kOrbLevels, (uint32_t)kFastT, n * kOrbLevels);
+        hipLaunchKernelGGL(k_fill_u32, dim3((n * kOrbLevels + 255) / 256), dim3(256), 0, st, tau, tau_first,
+                           (uint32_t)kFastT, n * kOrbLevels);
         hipLaunchKernelGGL(k_fast, dim3((unsigned)g.total_tiles * (unsigned)n), dim3(kFastThreads), 0, st, g, src, d_pyr_,
                            d_cand_cnt_, d_cand_, d_cand_sc_, d_cmap_);
       } else {
@@ -2678,7 +2675,7 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
     }
   }
   if (g.total_tiles > 0 && !dense) {
-    hipLaunchKernelGGL(k_fast_check, dim3((unsigned)n * kOrbLevels), dim3(64), 0, st, g, src.slot0, n, tau, tau_first,
+    hipLaunchKernelGGL(k_fast_check, dim3((unsigned)n * kOrbLevels), dim3(64), 0, st, g, n, tau, tau_first,
                        d_cand_cnt_, d_cand_sc_, d_cmap_, d_redo_, d_redo_ + 1, d_qstat_);
     // fixed grid (a multiple of 8: see the XCD-contiguous unit order), sized to what the batch could need
     long long units = (long long)n * kOrbLevels * g.max_level_tiles;
@@ -2690,7 +2687,7 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
     hipLaunchKernelGGL(k_fast_redo, dim3(grid), dim3(kFastThreads), 0, st, g, src, d_pyr_, d_redo_, d_redo_ + 1,
                        g.max_level_tiles, d_cand_cnt_, d_cand_, d_cand_sc_, d_cmap_, d_redo_hist_, (const uint32_t*)nullptr);
     hipLaunchKernelGGL(k_redo_thr, dim3((unsigned)std::min<long long>((long long)n * kOrbLevels, 1024)), dim3(64), 0, st, g,
-                       src.slot0, d_redo_, d_redo_ + 1, d_cmap_, d_redo_hist_, d_redo_thr_);
+                       d_redo_, d_redo_ + 1, d_cmap_, d_redo_hist_, d_redo_thr_);
     hipLaunchKernelGGL(k_fast_redo, dim3(grid), dim3(kFastThreads), 0, st, g, src, d_pyr_, d_redo_, d_redo_ + 1,
                        g.max_level_tiles, d_cand_cnt_, d_cand_, d_cand_sc_, d_cmap_, (uint32_t*)nullptr, d_redo_thr_);
   }
@@ -2702,7 +2699,6 @@ hipError_t OrbPipeline::extract_range(const FrameSrc& src, int n, hipStream_t st
 
 void OrbPipeline::launch_resize(const FrameSrc& src, int n, int l, hipStream_t st) {
   const OrbGeometry& g = g_;
-  uint8_t* const d_pyr_ = this->d_pyr_ - (ptrdiff_t)src.slot0 * g.pyr_bytes;   // work rows: see extract_range
   const OrbLevelInfo& L = g.lv[l];
   // band height: 8 output rows x 256 threads measured best (rth 4: 3.26 ms, 8: 2.71, 12: 2.77, 16: 2.74 per 2048
   // [r02, table-driven kernel: 12 or 16 rows on the small levels only: 2.65 vs 2.65-2.73, within run-to-run noise]
@@ -2723,12 +2719,6 @@ void OrbPipeline::launch_resize(const FrameSrc& src, int n, int l, hipStream_t s
 
 void OrbPipeline::launch_tail(const FrameSrc& src, int n, bool dense, hipStream_t st, hipEvent_t* evs, const uint32_t* fin) {
   const OrbGeometry& g = g_;
-  const ptrdiff_t back = (ptrdiff_t)src.slot0;                 // work rows: see extract_range
-  uint8_t* const d_pyr_ = this->d_pyr_ - back * g.pyr_bytes;
-  uint32_t* const d_cand_cnt_ = this->d_cand_cnt_ - back * kOrbLevels;
-  uint2* const d_cmap_ = this->d_cmap_ - back * kOrbLevels;
-  uint32_t* const d_s1_cnt_ = this->d_s1_cnt_ - back * kOrbLevels;
-  uint4* const d_s1_ = this->d_s1_ - back * g.s1_total;
   hipLaunchKernelGGL(k_thr_harris, dim3(g.nlevels, n), dim3(dense ? 256 : 64), 0, st, g, src, d_pyr_,
                      d_cand_cnt_, d_cand_, d_cand_sc_, d_cmap_, d_s1_cnt_, d_s1_, d_status_, dense ? 1 : 0, fin);
   if (!dense) {
@@ -2771,13 +2761,13 @@ hipError_t OrbPipeline::tail(const FrameSrc& src, int n, const int32_t* counts, 
   last_dense_ = true;      // MSF_DBG_FAST_CANDS returns the lists as they stand
   hipError_t e;
   if ((e = hipMemsetAsync(d_status_ + src.slot0, 0, (size_t)n * 4, st))) return e;
-  hipLaunchKernelGGL(k_cand_reset, dim3((n * kOrbLevels + 255) / 256), dim3(256), 0, st, g, prim_, this->d_cmap_, n, dense ? 1 : 0);
+  hipLaunchKernelGGL(k_cand_reset, dim3((n * kOrbLevels + 255) / 256), dim3(256), 0, st, g, prim_, d_cmap_, n, dense ? 1 : 0);
   hipLaunchKernelGGL(k_fill_u32, dim3((n * kOrbLevels + 255) / 256), dim3(256), 0, st, d_tau_,
                      d_tau_ + (size_t)work_frames_ * kOrbLevels, (uint32_t)kFastT, n * kOrbLevels);
   for (int l = 1; l < g.nlevels; l++) launch_resize(src, n, l, st);
   // the lists go where k_cand_reset has just put them: asked of the device, not restated here
   std::vector<uint2> cmap((size_t)n * kOrbLevels);
-  if ((e = hipMemcpyAsync(cmap.data(), this->d_cmap_, cmap.size() * sizeof(uint2), hipMemcpyDeviceToHost, st))) return e;
+  if ((e = hipMemcpyAsync(cmap.data(), d_cmap_, cmap.size() * sizeof(uint2), hipMemcpyDeviceToHost, st))) return e;
   if ((e = hipStreamSynchronize(st))) return e;
   size_t total = 0;
   for (int i = 0; i < n * kOrbLevels; i++) total += (size_t)counts[i];
@@ -2799,7 +2789,7 @@ hipError_t OrbPipeline::tail(const FrameSrc& src, int n, const int32_t* counts, 
     }
     off += cnt[i];
   }
-  if (!e) e = hipMemcpyAsync(this->d_cand_cnt_, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice, st);
+  if (!e) e = hipMemcpyAsync(d_cand_cnt_, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice, st);
   if (!e) {
     launch_tail(src, n, form == 0, st, nullptr, nullptr);   // the caller's lists: no level was finished by a walker
     e = hipGetLastError();
@@ -2974,37 +2964,36 @@ int OrbPipeline::debug_get(int what, int slot, int level, void* host_out, size_t
       if (cut > 0u) {
         const OrbLevelInfo& L = g.lv[level];
         const size_t cap_l = (size_t)L.cand_cap;
-        DevBuf<uint32_t> d_tmp;      // [2] queue (count, item) | [8] counts | [8] uint2 map | keys [cap_l] | scores [cap_l]
-        const size_t words = 2 + kOrbLevels + 2 * kOrbLevels + cap_l + (cap_l + 3) / 4;
-        if (d_tmp.reserve(words * 4) != hipSuccess) return fail("hipMalloc failed in debug_get");
-        if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize failed in debug_get");
-        uint32_t head[2 + kOrbLevels + 2 * kOrbLevels] = {};
+        // a queue of one entry and, as the kernel indexes them, one row of counts and of the list map per frame of the last
+        // call (all empty but this level's, whose list is the whole of the key / score buffers)
+        const size_t rows = (size_t)last_n_ * kOrbLevels, item = (size_t)row * kOrbLevels + level;
+        std::vector<uint32_t> head(2 + 3 * rows, 0u);   // [2] queue (count, item) | [rows] counts | [rows] uint2 map
         head[0] = 1u;
-        head[1] = (uint32_t)(row * kOrbLevels + level);
-        head[2 + kOrbLevels + 2 * level] = (uint32_t)(2 + 3 * kOrbLevels);        // the list starts right behind the map
-        head[2 + kOrbLevels + 2 * level + 1] = (uint32_t)cap_l;
-        hipMemcpy(d_tmp, head, sizeof(head), hipMemcpyHostToDevice);
-        // the kernels index per-(frame, level) arrays by slot = slot0 + frame: bases moved back by `slot` entries
-        const ptrdiff_t back = (ptrdiff_t)slot * kOrbLevels;
-        uint32_t* const cnt = d_tmp + 2 - back;
-        const uint2* const map = reinterpret_cast<const uint2*>(d_tmp + 2 + kOrbLevels) - back;
-        uint32_t* const keys = d_tmp;                                             // map entries are absolute offsets
-        uint8_t* const scs = reinterpret_cast<uint8_t*>(d_tmp + 2 + 3 * kOrbLevels + cap_l) - (2 + 3 * kOrbLevels);
-        const uint8_t* const pyr = d_pyr_ - (ptrdiff_t)last_src_.slot0 * g.pyr_bytes;
+        head[1] = (uint32_t)item;
+        head[2 + rows + 2 * item + 1] = (uint32_t)cap_l;                           // map entry (0, cap_l)
+        DevBuf<uint32_t> d_head, d_keys;
+        DevBuf<uint8_t> d_scs;
+        if (d_head.reserve(head.size() * 4) != hipSuccess || d_keys.reserve(cap_l * 4) != hipSuccess ||
+            d_scs.reserve(cap_l) != hipSuccess)
+          return fail("hipMalloc failed in debug_get");
+        if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize failed in debug_get");
+        hipMemcpy(d_head, head.data(), head.size() * 4, hipMemcpyHostToDevice);
+        uint32_t* const cnt = d_head + 2;
+        const uint2* const map = reinterpret_cast<const uint2*>(d_head + 2 + rows);
         const int tiles = L.tiles_x * L.tiles_y;
         if (tiles > 0)
           hipLaunchKernelGGL(k_fast_redo, dim3((unsigned)((std::min(tiles, 2048) + 7) & ~7)), dim3(kFastThreads), 0, 0, g,
-                             last_src_, pyr, d_tmp, d_tmp + 1, tiles, cnt, keys, scs, map, (uint32_t*)nullptr,
+                             last_src_, d_pyr_, d_head, d_head + 1, tiles, cnt, d_keys, d_scs, map, (uint32_t*)nullptr,
                              (const uint32_t*)nullptr);
         hipError_t e2 = hipDeviceSynchronize();
         n = 0;
-        if (e2 == hipSuccess) e2 = hipMemcpy(&n, d_tmp + 2 + level, 4, hipMemcpyDeviceToHost);
+        if (e2 == hipSuccess) e2 = hipMemcpy(&n, cnt + item, 4, hipMemcpyDeviceToHost);
         if (n > (uint32_t)cap_l) n = (uint32_t)cap_l;
         tk.assign(n, 0u);
         ts.assign(n, 0u);
         if (e2 == hipSuccess && n) {
-          e2 = hipMemcpy(tk.data(), d_tmp + 2 + 3 * kOrbLevels, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-          if (e2 == hipSuccess) e2 = hipMemcpy(ts.data(), d_tmp + 2 + 3 * kOrbLevels + cap_l, n, hipMemcpyDeviceToHost);
+          e2 = hipMemcpy(tk.data(), d_keys, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+          if (e2 == hipSuccess) e2 = hipMemcpy(ts.data(), d_scs, n, hipMemcpyDeviceToHost);
         }
         if (e2 != hipSuccess) return fail("dense FAST pass failed in debug_get");
       }

@@ -20,12 +20,13 @@ namespace msf {
 // The level plan, its structs (kernel arguments) and the capacities: orb_plan.h.
 constexpr int kOrbStages = 6;
 
-// where level 0 of slot s lives: slot < n_a ? a + slot*frame_stride : b + (slot-n_a)*frame_stride
+// where level 0 of frame fi of the call lives: fi < n_a ? a + fi*frame_stride : b + (fi-n_a)*frame_stride.
+// Two index spaces: the per-call arrays (work rows) are indexed by fi, the per-slot arrays by slot = slot0 + fi.
 struct FrameSrc {
   const uint8_t* a;
   const uint8_t* b;
   int n_a;
-  int slot0;               // first feature slot written by this call
+  int slot0;               // first feature slot written by this call: frame fi's key points go to slot slot0 + fi
   long long frame_stride;
   int row_stride;
 };
@@ -88,11 +89,12 @@ class OrbPipeline {
   int stream_min_frames_ = 8;      // calls with fewer frames take the dense FAST kernel (latency), others the streaming pass
   int force_tau_ = 0;              // > 0: every (frame, level) starts at this FAST score threshold (20 = dense)
   // device storage
-  // per CALL (work_frames_ rows): pyramid, candidate lists, thresholds, walker state, stage-1 lists
+  // per CALL (work_frames_ rows, indexed by the frame of the call): pyramid, candidate lists, thresholds, walker state,
+  // stage-1 lists
   DevBuf<uint8_t> d_pyr_;
   DevBuf<uint32_t> d_tab_;      // resize tables per level: per group of 4 columns selectors / weights / pair offsets, per row source row | w1 << 16
   bool resize_shared_[kOrbLevels] = {};   // OrbPlan::resize_shared
-  DevBuf<uint32_t> d_qstat_;           // [slots][levels][kQStat]: per (slot, level) the score histogram of the sampled quarter's
+  DevBuf<uint32_t> d_qstat_;           // [work rows][levels][kQStat]: per (frame, level) the score histogram of the sampled quarter's
                                           // corners, the thresholds and the done counters of the walker launch (see k_walk)
   DevBuf<uint32_t> d_walk_abort_;      // [4] the walker launch's abort word (a unit gave up waiting); zeroed per call
   uint32_t* h_walk_abort_ = nullptr;      // pinned copy of it, written behind every walker launch, read by later calls
@@ -109,17 +111,17 @@ class OrbPipeline {
   int test_stall_frame_ = -1;             // MSF_TEST_HOOKS + MSF_ORB_TEST_STALL_FRAME: see k_walk
   int tau2_margin_pct_ = 200;             // MSF_ORB_TAU2_MARGIN_PCT
   bool resize_generic_ = false;           // MSF_ORB_RESIZE_GENERIC: never
-  DevBuf<uint32_t> d_cand_cnt_; // [slots][8]
-  DevBuf<uint32_t> d_tau_;      // [2][slots][8] FAST score threshold used per (slot, level) | first estimate
-  DevBuf<uint32_t> d_redo_;     // [1 + slots * 8] dense-pass queue: count, entries (frame * 8 + level)
+  DevBuf<uint32_t> d_cand_cnt_; // [work rows][8]
+  DevBuf<uint32_t> d_tau_;      // [2][work rows][8] FAST score threshold used per (frame, level) | first estimate
+  DevBuf<uint32_t> d_redo_;     // [1 + work rows * 8] dense-pass queue: count, entries (frame * 8 + level)
   DevBuf<uint32_t> d_redo_hist_;  // [work rows][8][256] dense pass: score histogram of a queued level's maxima (kept zeroed)
   DevBuf<uint32_t> d_redo_thr_;   // [work rows][8] dense pass: the level's retainBest(2N) cut (k_redo_thr)
   DevBuf<uint32_t> d_cand_;     // [work rows][prim_total] + pool (dense calls): key = y << 16 | x
   DevBuf<uint8_t> d_cand_sc_;   // the same shape: FAST score
   DevBuf<uint2> d_cmap_;        // [work rows][8] where the list of (frame, level) lives: (first entry, capacity); reset per call
-  DevBuf<uint32_t> d_s1_cnt_;   // [slots][8]
-  DevBuf<uint4> d_s1_;          // [slots][s1_total] (key, response bits, score, 0)
-  // per feature SLOT (max_slots_): what a later match reads
+  DevBuf<uint32_t> d_s1_cnt_;   // [work rows][8]
+  DevBuf<uint4> d_s1_;          // [work rows][s1_total] (key, response bits, score, 0)
+  // per feature SLOT (max_slots_ rows, indexed by slot = slot0 + frame): what a later match reads
   DevBuf<msf_keypoint> d_kp_;   // [slots][kKpCap]
   DevBuf<uint8_t> d_desc_;      // [slots][kKpCap][32]
   DevBuf<uint32_t> d_kp_cnt_;   // [slots]

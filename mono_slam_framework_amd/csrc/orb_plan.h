@@ -90,8 +90,8 @@ struct OrbGeometry {
   // lays its frames' full-capacity regions over the pool (sized for that by plan_orb).
   long long pool_base;     // first pool entry
   unsigned pool_entries;
-  int s1_total;            // stage-1 entries per slot
-  long long pyr_bytes;     // pyramid blob bytes per slot (levels 1..)
+  int s1_total;            // stage-1 entries per work row
+  long long pyr_bytes;     // pyramid blob bytes per work row (levels 1..)
   OrbLevelInfo lv[kOrbLevels];
   int umax[16];
 };
