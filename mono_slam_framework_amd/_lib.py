@@ -5,6 +5,7 @@ import os
 import numpy as np
 
 from . import build as _build
+from . import results
 
 MSF_OK = 0
 MSF_ERR_INVALID_ARG = -1
@@ -83,11 +84,22 @@ class Image(C.Structure):
     _fields_ = [("data", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("stride", C.c_int64)]
 
 
+# msf_ransac_result's arrays in declaration order (rows as in the tables below): the homography's result has no fn, the
+# fundamental's no m12; best starts at -1
+RANSAC_ARRAYS = [("m21", "float32", "hyp", (3, 3)), ("m12", "float32", "hyp", (3, 3)), ("fn", "float32", "hyp", (3, 3)),
+                 ("null_vec", "float32", "hyp", (3, 3)), ("scores", "float32", "hyp", ()), ("best", "int32", "list", ()),
+                 ("best_inliers", "uint8", "list", ("cap",)), ("T1", "float32", "list", (3, 3)),
+                 ("T2", "float32", "list", (3, 3))]
+
+
 class RansacResult(C.Structure):
     """msf_ransac_result: host pointers for msf_find_models, device pointers inside a RansacBatch"""
-    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("m21", C.c_void_p), ("m12", C.c_void_p),
-                ("fn", C.c_void_p), ("null_vec", C.c_void_p), ("scores", C.c_void_p), ("best", C.c_void_p),
-                ("best_inliers", C.c_void_p), ("T1", C.c_void_p), ("T2", C.c_void_p)]
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(a[0], C.c_void_p) for a in RANSAC_ARRAYS]
+
+
+def ransac_shapes(lists, n_hyp, cap):
+    """-> {name: (shape, dtype name)} of msf_ransac_result's arrays"""
+    return results.shapes(RANSAC_ARRAYS, {"list": (lists,), "hyp": (lists, n_hyp)}, cap)
 
 
 class RansacBatch(C.Structure):
@@ -103,11 +115,11 @@ class MotionParams(C.Structure):
 
 # The result structs' arrays in declaration order: (name, dtype, per, trailing shape) with `per` the leading unit after
 # [n_lists] ("list": none) and "cap" the lists' stride; csrc/result_arrays.h holds the same tables for the library
-# (tests/test_result_arrays_host.py compares them).
-MOTION_ARRAYS = [("ok", "int32", "list", ()), ("model", "int32", "list", ()), ("R21", "float32", "list", (9,)),
+# (tests/test_result_arrays_host.py compares them).  A 3 x 3 matrix is (3, 3) here and nine floats there.
+MOTION_ARRAYS = [("ok", "int32", "list", ()), ("model", "int32", "list", ()), ("R21", "float32", "list", (3, 3)),
                  ("t21", "float32", "list", (3,)), ("points", "float32", "list", ("cap", 3)),
                  ("triangulated", "uint8", "list", ("cap",)), ("n_cand", "int32", "list", ()),
-                 ("cand_R", "float32", "list", (8, 9)), ("cand_t", "float32", "list", (8, 3)),
+                 ("cand_R", "float32", "list", (8, 3, 3)), ("cand_t", "float32", "list", (8, 3)),
                  ("cand_good", "int32", "list", (8,)), ("cand_parallax", "float32", "list", (8,)),
                  ("winner", "int32", "list", ())]
 
@@ -115,6 +127,11 @@ MOTION_ARRAYS = [("ok", "int32", "list", ()), ("model", "int32", "list", ()), ("
 class MotionResult(C.Structure):
     """msf_motion_result: host pointers for msf_reconstruct, device pointers [n_lists] for msf_reconstruct_device"""
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(a[0], C.c_void_p) for a in MOTION_ARRAYS]
+
+
+def list_shapes(table, lists, cap):
+    """-> {name: (shape, dtype)} of msf_motion_result's (MOTION_ARRAYS) or msf_new_points_result's (NEW_POINTS_ARRAYS) arrays"""
+    return results.shapes(table, {"list": (lists,)}, cap)
 
 
 class View(C.Structure):
@@ -167,8 +184,7 @@ class PnpResult(C.Structure):
 
 def pnp_shapes(lists, n_iterations, max_records, cap):
     """-> {name: (shape, dtype name)} of msf_pnp_result's arrays"""
-    lead = {"list": (lists,), "hyp": (lists, n_iterations), "rec": (lists, max_records)}
-    return {name: (lead[per] + tuple(cap if t == "cap" else t for t in tail), dt) for name, dt, per, tail in PNP_ARRAYS}
+    return results.shapes(PNP_ARRAYS, {"list": (lists,), "hyp": (lists, n_iterations), "rec": (lists, max_records)}, cap)
 
 
 class PoseParams(C.Structure):
@@ -194,8 +210,7 @@ class PoseResult(C.Structure):
 
 def pose_shapes(lists, cap):
     """-> {name: (shape, dtype name)} of msf_pose_result's arrays"""
-    lead = {"list": (lists,), "round": (lists, 4), "it": (lists, 4, 10)}
-    return {name: (lead[per] + tuple(cap if t == "cap" else t for t in tail), dt) for name, dt, per, tail in POSE_ARRAYS}
+    return results.shapes(POSE_ARRAYS, {"list": (lists,), "round": (lists, 4), "it": (lists, 4, 10)}, cap)
 
 
 class BaParams(C.Structure):
@@ -232,7 +247,7 @@ def ba_shapes(problems, cams, points, edges):
     flat [64 * cams] ([64 * points]) rows and is [64][n_cams] ([64][n_points])."""
     lead = {"problem": (problems,), "cam": (cams,), "point": (points,), "edge": (edges,), "round": (problems, 2),
             "it": (problems, BA_SLOTS), "it_cam": (BA_SLOTS * cams,), "it_point": (BA_SLOTS * points,)}
-    return {name: (lead[per] + tuple(tail), dt) for name, dt, per, tail in BA_ARRAYS}
+    return results.shapes(BA_ARRAYS, lead)
 
 
 class LocalMap(C.Structure):
@@ -281,8 +296,7 @@ class ClaimResult(C.Structure):
 
 def tracking_shapes(table, points, kfs, cap, corr_cap):
     """-> {name: (shape, dtype)} of msf_frustum_result's (FRUSTUM_ARRAYS) or msf_claim_result's (CLAIM_ARRAYS) arrays"""
-    lead = {"call": (1,), "point": (points,), "kf": (kfs,), "corr": (corr_cap,)}
-    return {name: (lead[per] + tuple(cap if t == "cap" else t for t in tail), dt) for name, dt, per, tail in table}
+    return results.shapes(table, {"call": (1,), "point": (points,), "kf": (kfs,), "corr": (corr_cap,)}, cap)
 
 
 VIEW_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4")])

@@ -47,16 +47,7 @@ def run(L, sc, schedule, stop=None, huber_delta2=5.991, chi2=5.991, max_free=64,
 
 
 def shape_result(d, nc, npt):
-    """the flat arrays of one problem as [64][n_cams] / [64][n_points] blocks, status as an int"""
-    out = dict(d)
-    out["status"] = int(d["status"][0])
-    out["round_iterations"] = d["round_iterations"][0]
-    for k, v in d.items():
-        if k.startswith("it_"):
-            if v.shape[0] == 64 * nc and k in ("it_cam_in", "it_cam_out", "it_Hcc", "it_bc"):
-                out[k] = v.reshape((64, nc) + v.shape[1:])
-            elif k in ("it_point_in", "it_point_out", "it_Hpp", "it_bp"):
-                out[k] = v.reshape((64, npt) + v.shape[1:])
-            else:
-                out[k] = v[0]
-    return out
+    """the flat arrays of one problem as [64][n_cams] / [64][n_points] blocks, status as an int: the view that
+    _Matcher.bundle_adjust returns of them"""
+    from mono_slam_framework_amd import _lib, results
+    return results.view_ba(d, _lib.BA_ARRAYS, _lib.BA_SLOTS, nc, npt)
