@@ -1,4 +1,4 @@
-"""ctypes view of include/msf_abi.h, include/msf_initializer.h, include/msf_local_mapping.h, include/msf_pnp.h, include/msf_pose.h, include/msf_ba.h, include/msf_global_ba.h and include/msf_tracking.h.  Loading fails loudly when libmsf.so is missing: there is no CPU fallback."""
+"""ctypes view of include/msf_abi.h, include/msf_initializer.h, include/msf_local_mapping.h, include/msf_pnp.h, include/msf_pose.h, include/msf_ba.h, include/msf_global_ba.h, include/msf_tracking.h and include/msf_frame_tracking.h.  Loading fails loudly when libmsf.so is missing: there is no CPU fallback."""
 import ctypes as C
 import os
 
@@ -72,6 +72,13 @@ TRACKING_SYMBOLS = ["msf_tracking_version", "msf_frustum", "msf_frustum_device",
                     "msf_search_local_points"]
 MSF_POINT_BAD, MSF_POINT_SEEN = 1, 2
 MSF_SEARCH_KEEP_ON_DEVICE = 1
+
+# every symbol include/msf_frame_tracking.h declares.  The msf_ names are closed with msf_tracking.h: the entry points of
+# every later header carry the prefix msfx_
+FRAME_TRACKING_SYMBOLS = ["msfx_frame_tracking_version", "msfx_carry_points_device", "msfx_track_list_device",
+                          "msfx_track_frame"]
+MSFX_TRACK_MAX_CANDIDATES = 8192
+MSFX_TRACK_KEEP_ON_DEVICE = 1
 
 
 class Config(C.Structure):
@@ -299,6 +306,49 @@ def tracking_shapes(table, points, kfs, cap, corr_cap):
     return results.shapes(table, {"call": (1,), "point": (points,), "kf": (kfs,), "corr": (corr_cap,)}, cap)
 
 
+class FrameMap(C.Structure):
+    """msfx_frame_map: host pointers for msfx_track_frame, device pointers for the *_device calls"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_points", C.c_int32), ("n_ref", C.c_int32),
+                ("n_cur", C.c_int32), ("reserved2", C.c_int32), ("points", C.c_void_p), ("observed", C.c_void_p),
+                ("ref_key", C.c_void_p), ("ref_point", C.c_void_p), ("cur_key", C.c_void_p), ("cur_point", C.c_void_p)]
+
+
+class TrackParams(C.Structure):
+    """msfx_track_params: the optimiser's parameters, the entry pose and the two thresholds"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("pose", PoseParams), ("Tcw0", C.c_float * 12),
+                ("min_matches", C.c_int32), ("min_map_matches", C.c_int32)]
+
+
+FRAME_POINT_DTYPE = np.dtype([("key", "<i4"), ("point", "<i4"), ("match", "<i4"), ("flags", "<i4")])
+REMOVED_POINT_DTYPE = np.dtype([("key", "<i4"), ("point", "<i4")])
+# msfx_track_result's arrays in declaration order: (name, dtype, per "call" / "match" / "cur" / "corr", trailing shape);
+# csrc/frame_tracking_arrays.h holds the same table (tests/test_frame_tracking_arrays_host.py compares them)
+TRACK_ARRAYS = [("track_status", "int32", "call", ()), ("n_map", "int32", "call", ()), ("map", FRAME_POINT_DTYPE, "corr", ()),
+                ("carry_status", "uint8", "match", ()), ("cur_status", "uint8", "cur", ()),
+                ("corr_p3d", "float32", "corr", (3,)), ("corr_p2d", "float32", "corr", (2,)), ("corr_point", "int32", "corr", ()),
+                ("Tcw", "float32", "call", (12,)), ("n_good", "int32", "call", ()), ("n_kept", "int32", "call", ()),
+                ("kept_key", "int32", "corr", ()), ("kept_point", "int32", "corr", ()), ("n_removed", "int32", "call", ()),
+                ("removed", REMOVED_POINT_DTYPE, "corr", ()), ("n_matches_map", "int32", "call", ())]
+CARRY_NAMES = tuple(a[0] for a in TRACK_ARRAYS[:8])   # what msfx_carry_points_device writes
+
+
+class TrackResult(C.Structure):
+    """msfx_track_result: device pointers for the *_device calls, host pointers for msfx_track_frame"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(a[0], C.c_void_p) for a in TRACK_ARRAYS]
+
+
+class DeviceTrack(C.Structure):
+    """msfx_device_track: where msfx_track_frame left its results with MSFX_TRACK_KEEP_ON_DEVICE"""
+    _fields_ = [("struct_size", C.c_uint32), ("corr_cap", C.c_int32)] + [(n, C.c_void_p) for n in (
+        "d_track_status", "d_n_kept", "d_kept_key", "d_kept_point", "d_n_map", "d_corr_p3d", "d_corr_p2d", "d_corr_point",
+        "d_outliers", "d_Tcw")]
+
+
+def track_shapes(cap, n_cur, corr_cap):
+    """-> {name: (shape, dtype)} of msfx_track_result's arrays; "call" arrays are [1, ...]"""
+    return results.shapes(TRACK_ARRAYS, {"call": (1,), "match": (cap,), "cur": (n_cur,), "corr": (corr_cap,)})
+
+
 VIEW_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4")])
 MATCH_DTYPE = np.dtype([("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4")])
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("response", "<f4"), ("angle", "<f4"),
@@ -379,6 +429,12 @@ def load():
     L.msf_claim_points_device.argtypes = [vp, C.POINTER(LocalMap), vp, i32, vp, vp, i32, C.POINTER(ClaimResult), vp]
     L.msf_search_local_points.argtypes = [vp, i32, vp, C.POINTER(LocalMap), C.POINTER(FrustumParams), C.c_uint32, vp, vp,
                                           i32, C.POINTER(FrustumResult), C.POINTER(ClaimResult), C.POINTER(DeviceCorr)]
+    L.msfx_frame_tracking_version.restype = C.c_int
+    L.msfx_carry_points_device.argtypes = [vp, C.POINTER(FrameMap), vp, i32, vp, i32, C.POINTER(TrackResult), vp]
+    L.msfx_track_list_device.argtypes = [vp, C.POINTER(FrameMap), vp, i32, vp, i32, C.POINTER(TrackParams),
+                                         C.POINTER(TrackResult), C.POINTER(PoseResult), vp]
+    L.msfx_track_frame.argtypes = [vp, i32, i32, C.POINTER(FrameMap), C.POINTER(TrackParams), C.c_uint32, vp, vp, i32,
+                                   C.POINTER(TrackResult), C.POINTER(PoseResult), C.POINTER(DeviceTrack)]
     L.msf_render_match_image.argtypes = [vp, C.POINTER(Image), C.POINTER(Image), vp, i32, vp, vp, vp, i64]
     L.msf_weights_info.argtypes = [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(i64)]
     L.msf_convert_weights.argtypes = [C.c_char_p, C.c_char_p]

@@ -11,7 +11,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 HIP_SOURCES = ["msf_abi.cpp", "msf_multi.cpp", "msf_gather.cpp", "weights_io.cpp", "orb_kernels.hip", "loftr_kernels.hip", "pack_kernels.hip",
                "ransac_kernels.hip", "reconstruct_kernels.hip", "triangulate_kernels.hip", "pnp_kernels.hip", "pose_kernels.hip",
-               "ba_kernels.hip", "gba_kernels.hip", "tracking_kernels.hip"]
+               "ba_kernels.hip", "gba_kernels.hip", "tracking_kernels.hip", "frame_tracking_kernels.hip"]
 # -ffp-contract=off + correctly rounded f32 divide: the few f32 steps inside ORB
 # (Harris response, fastAtan2, pattern rotation) must round exactly like the CPU.
 # -mllvm -amdgpu-mfma-vgpr-form: MFMA results straight into VGPRs (the default put the accumulators of k_attn_update_x and
@@ -38,6 +38,7 @@ def _deps():
     d.append(os.path.join(ROOT, "include", "msf_ba.h"))
     d.append(os.path.join(ROOT, "include", "msf_global_ba.h"))
     d.append(os.path.join(ROOT, "include", "msf_tracking.h"))
+    d.append(os.path.join(ROOT, "include", "msf_frame_tracking.h"))
     return d
 
 

@@ -12,6 +12,10 @@
 //                    reference makes its SetMapPoint calls;
 //   TrackLocalMap()  chains Search() with MSF_SEARCH_KEEP_ON_DEVICE into msf::Optimizer::PoseOptimizationDevice: the
 //                    correspondences never leave the device, only the records, the pose and the flags come back.
+// In front of it stands the body of Tracking::TrackWithMotionModel / TrackReferenceKeyFrame (:434-485, :380-424;
+// include/msf_frame_tracking.h): the caller fills a FrameTracker with the train frame's map and the point table, and
+//   FrameTracker::Track()  is msfx_track_frame: match, carry, PoseOptimization and the cut in one call;
+//   TrackFrame()           chains it into TrackLocalMap(): the tracked-frame branch of Tracking::Track in two calls.
 // Header-only and OpenCV-free, like hip_local_mapping.h.  What stays with the caller: UpdateLocalKeyFrames, the first
 // loop of :576-592 (its result is cur_key / cur_point and the seen flags), IncreaseVisible from `visible`, SetMapPoint from
 // `claims`, IncreaseFound.  See INTEGRATION.md.
@@ -24,6 +28,7 @@
 #include "hip_device_block.h"
 #include "hip_mirror_types.h"
 #include "hip_optimizer.h"
+#include "msf_frame_tracking.h"
 #include "msf_tracking.h"
 
 namespace msf {
@@ -170,6 +175,105 @@ inline int TrackLocalMap(msf_handle* handle, int32_t query_slot, LocalPointSearc
   const float intrinsics[4] = {search.params.view.fx, search.params.view.fy, search.params.view.cx, search.params.view.cy};
   return Optimizer::PoseOptimizationDevice(handle, kept.d_corr_p3d, kept.d_corr_p2d, kept.corr_cap, kept.d_n_corr,
                                            intrinsics, Tcw, outliers, chi2);
+}
+
+// The body of Tracking::TrackWithMotionModel (train = the last frame, cur_* empty after Clear()) and of
+// TrackReferenceKeyFrame (train = the reference key frame; cur_* = what the frame holds when it runs as the fallback).
+class FrameTracker {
+ public:
+  // ---- in (include/msf_frame_tracking.h: msfx_frame_map, msfx_track_params) ----
+  std::vector<msf_map_point> points;         // the point table that goes on to LocalPointSearch; only pos is read here
+  std::vector<uint8_t> observed;             // [n_points]: Observations() > 0; empty: every point is observed
+  std::vector<int32_t> ref_key, ref_point;   // the train frame's mKeyPointMap, keys y * cols + x increasing
+  std::vector<int32_t> cur_key, cur_point;   // the current frame's own map at entry, keys increasing
+  float intrinsics[4] = {0, 0, 0, 0};        // fx, fy, cx, cy
+  float chi2 = 5.991f;
+  int32_t min_matches = 15, min_map_matches = 10;   // mMinLocalMatchCount, and the 10 of :422 / :483
+
+  // ---- out ----
+  int32_t track_status = -1;                 // 0 tracked, 1 too few matches, 2 too few map matches; negative: no result
+  int32_t num_matches = 0, n_good = -1, n_matches_map = 0;
+  std::vector<msfx_frame_point> map;         // the frame's map after the carry, key order; flags bit 0: removed by the cut
+  std::vector<int32_t> kept_key, kept_point; // the frame's map at return: LocalPointSearch::cur_key / cur_point
+  std::vector<msfx_removed_point> removed;   // SetMapPoint(key, nullptr); mnLastFrameSeen is still due to these points
+
+  // The stored frame query_slot against the stored frame train_slot.  Tcw in: the entry pose (row-major [16]; mVelocity *
+  // mLastFrame.mTcw, or the last frame's), out: the optimised pose when the call gave a result (track_status >= 0).
+  // `kept`: null, or where the results stay on the device (MSFX_TRACK_KEEP_ON_DEVICE).  true: the frame is tracked
+  // (track_status == 0).  false with track_status < 0: a failed call (msf_last_error(handle) has the text), a malformed
+  // map, no room or no valid list.
+  bool Track(msf_handle* handle, int32_t query_slot, int32_t train_slot, float Tcw[16], int32_t cap = 4096,
+             msfx_device_track* kept = nullptr) {
+    track_status = -1, num_matches = 0, n_good = -1, n_matches_map = 0;
+    map.clear(), kept_key.clear(), kept_point.clear(), removed.clear();
+    if (!handle || cap < 1 || ref_key.size() != ref_point.size() || cur_key.size() != cur_point.size() ||
+        (!observed.empty() && observed.size() != points.size()))
+      return false;
+    const size_t room = cur_key.size() + static_cast<size_t>(cap);
+    msfx_frame_map m = sized<msfx_frame_map>();
+    m.n_points = static_cast<int32_t>(points.size()), m.n_ref = static_cast<int32_t>(ref_key.size());
+    m.n_cur = static_cast<int32_t>(cur_key.size());
+    m.points = points.data(), m.observed = observed.empty() ? nullptr : observed.data();
+    m.ref_key = ref_key.data(), m.ref_point = ref_point.data(), m.cur_key = cur_key.data(), m.cur_point = cur_point.data();
+    msfx_track_params prm = sized<msfx_track_params>();
+    prm.pose = sized<msf_pose_params>();
+    prm.pose.fx = intrinsics[0], prm.pose.fy = intrinsics[1], prm.pose.cx = intrinsics[2], prm.pose.cy = intrinsics[3];
+    prm.pose.chi2 = chi2;
+    std::memcpy(prm.Tcw0, Tcw, sizeof prm.Tcw0);
+    prm.min_matches = min_matches, prm.min_map_matches = min_map_matches;
+    std::vector<msfx_frame_point> recs(room + 1);
+    std::vector<int32_t> keys(room + 1), pts(room + 1);
+    std::vector<msfx_removed_point> gone(room + 1);
+    int32_t counts[3] = {0, 0, 0};
+    float pose[12];
+    msfx_track_result out = sized<msfx_track_result>();
+    out.track_status = &track_status, out.n_map = &counts[0], out.map = recs.data();
+    out.Tcw = pose, out.n_good = &n_good, out.n_kept = &counts[1], out.kept_key = keys.data(), out.kept_point = pts.data();
+    out.n_removed = &counts[2], out.removed = gone.data(), out.n_matches_map = &n_matches_map;
+    if (kept) *kept = sized<msfx_device_track>();
+    const int rc = msfx_track_frame(handle, query_slot, train_slot, &m, &prm, kept ? MSFX_TRACK_KEEP_ON_DEVICE : 0u,
+                                    &num_matches, nullptr, cap, &out, nullptr, kept);
+    if (rc != MSF_OK || track_status < 0) {   // MSF_ERR_CAPACITY included: no valid list, as a failed MatchFrames
+      if (track_status >= 0) track_status = -1;
+      return false;
+    }
+    map.assign(recs.begin(), recs.begin() + counts[0]);
+    kept_key.assign(keys.begin(), keys.begin() + counts[1]);
+    kept_point.assign(pts.begin(), pts.begin() + counts[1]);
+    removed.assign(gone.begin(), gone.begin() + counts[2]);
+    std::memcpy(Tcw, pose, sizeof pose);
+    return track_status == 0;
+  }
+};
+
+// The tracked-frame branch of Tracking::Track (Tracking.cc:120-140): TrackWithMotionModel or TrackReferenceKeyFrame,
+// then TrackLocalMap.  tracker.Track() against train_slot; on success the frame's map at return becomes search's
+// cur_key / cur_point, the points of kept and removed alike get MSF_POINT_SEEN in search.points (the reference's
+// mnLastFrameSeen covers both, Tracking.cc:576-592 and :416), the current frame's view in search.params takes the new
+// pose -- mRcw, mtcw and mOw = -mRcw' mtcw, f32 products summed left to right as the solve headers do for a cv::Mat
+// product -- and TrackLocalMap() runs on search.slots.  search.points must be the table tracker.points indexes.
+// -> TrackLocalMap's count; -1: a call failed; -2: the frame was not tracked (tracker.track_status says why).
+inline int TrackFrame(msf_handle* handle, int32_t query_slot, int32_t train_slot, FrameTracker& tracker,
+                      LocalPointSearch& search, float Tcw[16], std::vector<bool>& outliers, int32_t cap = 4096,
+                      float chi2 = 5.991f) {
+  if (search.points.size() != tracker.points.size()) return -1;
+  tracker.chi2 = chi2;
+  if (!tracker.Track(handle, query_slot, train_slot, Tcw, cap)) return tracker.track_status < 0 ? -1 : -2;
+  search.cur_key = tracker.kept_key;
+  search.cur_point = tracker.kept_point;
+  for (int32_t p : tracker.kept_point) search.points[static_cast<size_t>(p)].flags |= MSF_POINT_SEEN;
+  for (const msfx_removed_point& r : tracker.removed) search.points[static_cast<size_t>(r.point)].flags |= MSF_POINT_SEEN;
+  msf_view& v = search.params.view;
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) v.Rcw[3 * r + c] = Tcw[4 * r + c];
+    v.tcw[r] = Tcw[4 * r + 3];
+  }
+  for (int c = 0; c < 3; c++) {
+    float sum = 0.0f;
+    for (int r = 0; r < 3; r++) sum += v.Rcw[3 * r + c] * v.tcw[r];
+    search.params.Ow[c] = -sum;
+  }
+  return TrackLocalMap(handle, query_slot, search, Tcw, outliers, cap, chi2);
 }
 
 }  // namespace msf

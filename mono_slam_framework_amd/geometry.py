@@ -336,6 +336,125 @@ class _Geometry:
             out.update(corr_p3d=cd["corr_p3d"][:k], corr_p2d=cd["corr_p2d"][:k], corr_point=cd["corr_point"][:k])
         return out
 
+    _FRAME_MAP_KEYS = ("points", "ref_key", "ref_point", "cur_key", "cur_point")
+
+    @staticmethod
+    def make_frame_map(points, ref_key, ref_point, cur_key=(), cur_point=(), observed=None):
+        """-> the inputs of one frame-tracking call (msfx_frame_map) as a dict of contiguous numpy arrays: points
+        MAP_POINT_DTYPE [n_points], ref_key / ref_point int32 [n_ref] (the train frame's mKeyPointMap), cur_key /
+        cur_point int32 [n_cur] (the current frame's own map at entry), observed uint8 [n_points] or None"""
+        i32 = lambda a: np.ascontiguousarray(np.asarray(a, np.int32).reshape(-1))
+        pts = np.ascontiguousarray(np.asarray(points, _lib.MAP_POINT_DTYPE).reshape(-1))
+        obs = None if observed is None else np.ascontiguousarray(np.asarray(observed, np.uint8).reshape(pts.size))
+        return dict(points=pts, ref_key=i32(ref_key), ref_point=i32(ref_point), cur_key=i32(cur_key),
+                    cur_point=i32(cur_point), observed=obs)
+
+    @classmethod
+    def frame_map_to_device(cls, fmap, device="cuda"):
+        """a make_frame_map dict -> the same with CUDA tensors (points as uint8 [n_points, 32])"""
+        import torch
+        out = {"observed": None if fmap["observed"] is None else torch.from_numpy(fmap["observed"].copy()).to(device)}
+        for k in cls._FRAME_MAP_KEYS:
+            a = fmap[k].view(np.uint8).reshape(-1, 32) if k == "points" else fmap[k]
+            out[k] = torch.from_numpy(a.copy()).to(device)
+        return out
+
+    @classmethod
+    def _frame_map(cls, fmap):
+        """-> msfx_frame_map over the dict's numpy arrays or CUDA tensors"""
+        ptr = lambda a: a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()
+        count = lambda a: a.size if isinstance(a, np.ndarray) else a.numel()
+        pts = fmap["points"]
+        n_points = pts.size if isinstance(pts, np.ndarray) else pts.numel() // 32
+        n_ref, n_cur = count(fmap["ref_key"]), count(fmap["cur_key"])
+        assert count(fmap["ref_point"]) == n_ref and count(fmap["cur_point"]) == n_cur
+        obs = fmap.get("observed")
+        assert obs is None or count(obs) == n_points
+        return _lib.FrameMap(struct_size=C.sizeof(_lib.FrameMap), n_points=n_points, n_ref=n_ref, n_cur=n_cur,
+                             observed=None if obs is None else ptr(obs), **{k: ptr(fmap[k]) for k in cls._FRAME_MAP_KEYS})
+
+    @classmethod
+    def _track_params(cls, K, Tcw0, chi2, min_matches, min_map_matches):
+        prm = _lib.TrackParams(struct_size=C.sizeof(_lib.TrackParams), pose=cls._pose_params(K, chi2),
+                               min_matches=min_matches, min_map_matches=min_map_matches)
+        prm.Tcw0[:] = [float(v) for v in np.asarray(Tcw0, np.float32).reshape(12)]
+        return prm
+
+    @staticmethod
+    def _device_list(d_matches, d_n_out):
+        """One list in device memory: d_matches int32 [cap, 4], d_n_out int32 [1] -> cap"""
+        import torch
+        assert d_matches.is_cuda and d_n_out.is_cuda and d_matches.is_contiguous() and d_n_out.numel() == 1
+        assert d_matches.dtype == torch.int32 and d_n_out.dtype == torch.int32 and d_matches.shape[1:] == (4,)
+        return d_matches.shape[0]
+
+    def carry_points_device(self, d_fmap, d_matches, d_n_out, corr_cap, out=None, stream=None):
+        """The carry of TrackWithMotionModel / TrackReferenceKeyFrame (Tracking.cc:448-459) on one list in device memory:
+        d_fmap a frame_map_to_device dict, d_matches int32 [cap, 4], d_n_out int32 [1].  -> dict of CUDA tensors named as
+        msfx_track_result says, up to corr_point: track_status [1] (0, -1 malformed map, -2 no room, -3 no list), n_map
+        [1], map int32 [corr_cap, 4] (key, point, match, flags; ascending key), carry_status uint8 [cap], cur_status
+        uint8 [n_cur], corr_* [corr_cap, ...].  `out`: tensors to write into instead of fresh zeros."""
+        cap = self._device_list(d_matches, d_n_out)
+        m = self._frame_map(d_fmap)
+        d = out
+        if d is None:
+            shapes = _lib.track_shapes(cap, m.n_cur, corr_cap)
+            d = alloc(shapes, d_matches.device, leave_out=set(shapes) - set(_lib.CARRY_NAMES))
+        self._check(self._L.msfx_carry_points_device(self._h, C.byref(m), d_matches.data_ptr(), cap, d_n_out.data_ptr(),
+                                                     corr_cap, C.byref(fill(_lib.TrackResult(), d)), stream))
+        return d
+
+    def track_list_device(self, d_fmap, d_matches, d_n_out, corr_cap, K, Tcw0, chi2=5.991, min_matches=15,
+                          min_map_matches=10, out=None, pose_out=None, diagnostics=False, stream=None):
+        """The body of TrackWithMotionModel / TrackReferenceKeyFrame behind the match (Tracking.cc:448-484) on one list
+        in device memory: carry, PoseOptimization from Tcw0, cut.  -> (dict of CUDA tensors named and shaped as
+        msfx_track_result says, dict of msf_pose_result's tensors for the one list with cap = corr_cap).  track_status
+        [1]: 0 tracked, 1 fewer than min_matches matches, 2 fewer than min_map_matches kept observed points, negative
+        as carry_points_device.  Three launches, asynchronous on `stream` (None = handle stream + sync)."""
+        cap = self._device_list(d_matches, d_n_out)
+        m = self._frame_map(d_fmap)
+        dev = d_matches.device
+        d = out if out is not None else alloc(_lib.track_shapes(cap, m.n_cur, corr_cap), dev)
+        pd = pose_out if pose_out is not None else self._pose_arrays(1, max(corr_cap, 1), diagnostics, dev)
+        prm = self._track_params(K, Tcw0, chi2, min_matches, min_map_matches)
+        self._check(self._L.msfx_track_list_device(self._h, C.byref(m), d_matches.data_ptr(), cap, d_n_out.data_ptr(),
+                                                   corr_cap, C.byref(prm), C.byref(fill(_lib.TrackResult(), d)),
+                                                   C.byref(fill(_lib.PoseResult(), pd)), stream))
+        return d, pd
+
+    def track_frame(self, query_slot, train_slot, fmap, K, Tcw0, chi2=5.991, min_matches=15, min_map_matches=10,
+                    cap=4096, keep_on_device=False, want_list=True, diagnostics=False):
+        """TrackWithMotionModel / TrackReferenceKeyFrame in one call: the stored frame query_slot against the stored
+        frame train_slot, fmap a make_frame_map dict.  -> dict: num_matches, list int32 [n, 4] (or None), capacity (True:
+        the list overflowed, as match_one_to_many reports it), track_status, n_map, map FRAME_POINT_DTYPE [n_map],
+        carry_status, cur_status, corr_p3d / corr_p2d / corr_point [n_map], Tcw [12], n_good, n_kept, kept_key / kept_point
+        [n_kept] (the cur_key / cur_point of the local map that goes on to search_local_points), n_removed, removed
+        REMOVED_POINT_DTYPE [n_removed], n_matches_map, pose (as pose_optimize returns it) -- and with keep_on_device
+        `keep`: the device addresses of msfx_device_track by name, valid until the next call of this family."""
+        m = self._frame_map(fmap)
+        corr_cap = m.n_cur + cap
+        num = np.zeros(1, np.int32)
+        lst = np.zeros(cap, _lib.MATCH_DTYPE) if want_list else None
+        d = alloc(_lib.track_shapes(cap, m.n_cur, corr_cap))
+        pd = self._pose_arrays(1, corr_cap, diagnostics)
+        keep = _lib.DeviceTrack(struct_size=C.sizeof(_lib.DeviceTrack))
+        prm = self._track_params(K, Tcw0, chi2, min_matches, min_map_matches)
+        rc = self._L.msfx_track_frame(self._h, query_slot, train_slot, C.byref(m), C.byref(prm),
+                                      _lib.MSFX_TRACK_KEEP_ON_DEVICE if keep_on_device else 0, num.ctypes.data,
+                                      lst.ctypes.data if want_list else None, cap, C.byref(fill(_lib.TrackResult(), d)),
+                                      C.byref(fill(_lib.PoseResult(), pd)), C.byref(keep) if keep_on_device else None)
+        if rc != _lib.MSF_ERR_CAPACITY:
+            self._check(rc)
+        n = min(max(int(num[0]), 0), cap)
+        out = results.view_track(d, n)
+        out.update(num_matches=int(num[0]), capacity=rc == _lib.MSF_ERR_CAPACITY, list=None,
+                   pose=results.view_pose(pd, max(out["n_map"], 0) if out["track_status"] in (0, 2) else 0))
+        if want_list:
+            out["list"] = lst[:n].view(np.int32).reshape(-1, 4).copy()
+        if keep_on_device:
+            out["keep"] = {name: getattr(keep, name) for name, _ in _lib.DeviceTrack._fields_[1:]}
+        return out
+
     @staticmethod
     def _pnp_params(K, th2, min_inliers, n_iterations, max_records, seed):
         fx, fy, cx, cy = K

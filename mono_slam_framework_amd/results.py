@@ -119,6 +119,19 @@ def view_frustum(d):
     return d
 
 
+def view_track(d, n_list):
+    """msfx_track_result on the host: the counts and the status as ints, every array cut to its count (carry_status to
+    the list's n_list matches); a negative track_status leaves the counts at 0 and the arrays empty"""
+    ints = ("track_status", "n_map", "n_good", "n_kept", "n_removed", "n_matches_map")
+    out = host_view({k: v for k, v in d.items() if k in ints or k == "Tcw"}, ints=ints)
+    ok = out["track_status"] >= 0
+    n_map, n_kept, n_removed = (out[k] if ok else 0 for k in ("n_map", "n_kept", "n_removed"))
+    cuts = dict(map=n_map, corr_p3d=n_map, corr_p2d=n_map, corr_point=n_map, kept_key=n_kept, kept_point=n_kept,
+                removed=n_removed, carry_status=n_list if out["track_status"] in (0, 2) else 0, cur_status=None if ok else 0)
+    out.update({k: d[k][:n] for k, n in cuts.items() if k in d})
+    return out
+
+
 def view_ba(d, table, slots, nc, npt):
     """One problem of msf_ba_result on the host: status as an int, round_iterations [2], the per-iteration arrays as
     [slots] / [slots, n_cams, ...] / [slots, n_points, ...]; everything else as it is."""
