@@ -103,6 +103,23 @@ def carry(fmap, matches, n, cap, corr_cap, min_matches=0):
                 corr_p3d=np.asarray(fmap["points"]["pos"], np.float32)[rec[:, 1]].reshape(-1, 3))
 
 
+def sorted_words(fmap, matches, n, cap):
+    """The valid words of the carry in ascending order, as the sort leaves them: [(key, rank)] with rank = c for entry c
+    of the frame and n_cur + j for candidate j of the list (a match with carry_status 0 or 4 in carry()'s own result).
+    Non-candidates carry no word.  Index i of this list is index i of the sorted words."""
+    n_cur = len(fmap["cur_key"])
+    c = carry(fmap, matches, n, cap, MAX_CANDIDATES)
+    assert c["status"] == 0, c["status"]
+    words = [(int(k), i) for i, k in enumerate(fmap["cur_key"])]
+    words += [(pixel_key(*matches[j][:2]), n_cur + j) for j in np.flatnonzero((c["carry_status"] == 0) | (c["carry_status"] == 4))]
+    return sorted(words)
+
+
+def runs_across(words, index):
+    """does a run of equal keys of sorted_words() hold both index - 1 and index?"""
+    return 0 < index < len(words) and words[index - 1][0] == words[index][0]
+
+
 def order_independent(fmap, matches, n, cap, corr_cap, min_matches, min_map_matches, optimise=no_optimiser, Tcw0=None):
     """The header's statement, steps 0-6.  -> the dict of carry() plus track_status, n_kept, kept_key, kept_point,
     n_removed, removed int32 [n_removed, 2], n_matches_map, outliers bool [n_map], and what `optimise` returned beside
@@ -126,6 +143,12 @@ def order_independent(fmap, matches, n, cap, corr_cap, min_matches, min_map_matc
     if out["status"] == 0:
         out["track_status"] = 0 if n_seen >= min_map_matches else 2
     return out
+
+
+def cut_chunks(outliers, chunk=256):
+    """-> [(kept, removed)] of every chunk of 256 records of the map, as the cut walks them"""
+    out = np.asarray(outliers).astype(bool)
+    return [(int((~out[i:i + chunk]).sum()), int(out[i:i + chunk].sum())) for i in range(0, len(out), chunk)]
 
 
 def agree(lit, oi):
@@ -200,6 +223,64 @@ def tied_case():
                         (300, 300, 9, 8), (301, 300, -1, 8), (302, 300, W, 8), (303, 300, 8, H),   # no point at k2
                         (200, 100, 9, 9)], np.int32)                                          # k1 on an entry, no point at k2: stays
     return fmap, matches
+
+
+BOUNDARY_RUNS = {1022: "emmm", 2047: "m", 3071: "em"}          # first sorted index -> the run there: e an entry, m a match
+BOUNDARY_WORDS = 4100
+
+
+def boundary_case():
+    """BOUNDARY_WORDS valid words laid out by sorted index: runs of one everywhere (an entry or a match, drawn) but for
+    BOUNDARY_RUNS -- four equal keys over the chunk edge at 1024, a run of one at the last index of the second chunk, a
+    run of two over the edge at 3072.  More than 4096 words, so the sort runs on 8192.  7 matches without k1 and 9
+    without a point at k2 are added and the list is shuffled with a fixed seed: rank order says nothing about key order.
+    -> (fmap, matches)"""
+    rng = np.random.default_rng(4096)
+    n_points, n_ref = 300, 500
+    pts = np.zeros(n_points, tr.MAP_POINT)
+    pts["pos"] = rng.uniform(-4, 4, (n_points, 3)).astype(np.float32)
+    layout, i = [], 0
+    while i < BOUNDARY_WORDS:
+        layout.append(BOUNDARY_RUNS.get(i, "e" if rng.random() < 0.4 else "m"))
+        i += len(layout[-1])
+    assert i == BOUNDARY_WORDS
+    keys = rng.choice(W * H, len(layout) + n_ref + 9, replace=False)
+    run_key = np.sort(keys[:len(layout)])
+    ref_key = np.sort(keys[len(layout):len(layout) + n_ref]).astype(np.int32)
+    no_entry = keys[len(layout) + n_ref:]                            # 9 pixels of the train frame without an entry
+    cur_key = np.array([k for k, run in zip(run_key, layout) if "e" in run], np.int32)
+    fmap = dict(points=pts, ref_key=ref_key, ref_point=rng.integers(0, n_points, n_ref).astype(np.int32), cur_key=cur_key,
+                cur_point=rng.integers(0, n_points, len(cur_key)).astype(np.int32),
+                observed=(rng.random(n_points) < 0.8).astype(np.uint8))
+    rows = []
+    for k, run in zip(run_key, layout):
+        for _ in range(run.count("m")):
+            k2 = int(rng.choice(ref_key))
+            rows.append((int(k) % W, int(k) // W, k2 % W, k2 // W))
+    k2 = int(ref_key[0])
+    rows += [(x, y, k2 % W, k2 // W) for x, y in ((-1, 5), (W, 5), (5, -1), (5, H), (-7, -7), (W + 1, H + 1), (0, H))]
+    rows += [(11 + i, 3, int(k) % W, int(k) // W) for i, k in enumerate(no_entry[:6])]
+    rows += [(21, 3, -1, 0), (22, 3, W, 0), (23, 3, 0, H)]
+    rows = np.array(rows, np.int32)
+    return fmap, rows[rng.permutation(len(rows))]
+
+
+def boundary_runs(fmap, matches):
+    """Proves from sorted_words() alone that boundary_case() reaches what it was built for: the three runs lie where
+    BOUNDARY_RUNS says, an entry first where it names one, and there are more than 4096 words.
+    -> {first index: the ranks of the run's words in sorted order}"""
+    n_cur, n = len(fmap["cur_key"]), len(matches)
+    words = sorted_words(fmap, matches, n, n)
+    assert 4096 < len(words) <= n_cur + n <= MAX_CANDIDATES                 # p2 = 8192: the 64 KiB block
+    runs = {}
+    for first, run in BOUNDARY_RUNS.items():
+        last = first + len(run) - 1
+        assert len(set(k for k, _ in words[first:last + 1])) == 1, first
+        assert words[first - 1][0] < words[first][0] and words[last][0] < words[last + 1][0], first   # no longer than that
+        ranks = [r for _, r in words[first:last + 1]]
+        assert [("e" if r < n_cur else "m") for r in ranks] == list(run), first
+        runs[first] = ranks
+    return runs
 
 
 def malformed(fmap):

@@ -2,7 +2,12 @@
 workgroup's chunk, a clipped list, the tied case and an empty frame map: the records, both status arrays, n_map and the
 correspondences are exactly those of tests/frame_tracking_ref.py and of the host build of csrc/frame_tracking_solve.h,
 and every byte beyond n_map (and beyond the list) is untouched.  A corr_cap one short answers -2, each malformed map -1,
-an invalid list -3, all without writing anything else.  A second call is bit-identical."""
+an invalid list -3, all without writing anything else.  A second call is bit-identical.
+
+Past one chunk of step 3 (more words than the workgroup has threads): totals on both sides of 1024, 2048, 4096 and at 8191
+and 8192, the two one-sided splits of 8192, 8193, a clipped list of 6000 and fr.boundary_case() -- runs of equal keys over
+the chunk edges, a last word that is no padding, the 64 KiB LDS block above 4096 words.  That the inputs reach these is
+asserted from fr.sorted_words first."""
 import numpy as np
 import pytest
 
@@ -85,6 +90,102 @@ def test_clipped_list_tied_case_and_empty_frame_map(fm, host):
     ref = fr.carry(empty, matches, 257, 330, 257)
     assert ref["status"] == 0 and 0 < ref["n_map"] < 257
     fh.check_carry(device_carry(fm, fm.frame_map_to_device(empty), matches, 257, 330, 0, 257), ref, "n_cur = 0")
+
+
+# ---- past one chunk of step 3: more words than the workgroup has threads, up to the 8192 of the interface ----------------
+
+# (n_cur, n): totals on both sides of 1024, 2048, 4096 (above it the sort takes the 64 KiB block) and at 8192, then the
+# two splits of 8192 words with one side empty
+EDGE_PAIRS = [(150, 873), (150, 874), (150, 875), (500, 1548), (500, 1549), (500, 3596), (500, 3597), (3000, 5191),
+              (3000, 5192), (0, 8192), (8192, 0)]
+SEED = 7
+_SCENES = {}
+
+
+def large_scene(n_cur, n):
+    """fr.scene over 3000 points and 6000 entries of the train frame, computed once per size"""
+    if (n_cur, n) not in _SCENES:
+        _SCENES[n_cur, n] = fr.scene(SEED, n_points=3000, n_ref=6000, n_cur=n_cur, n_matches=n)
+    return _SCENES[n_cur, n]
+
+
+def carry_three_ways(fm, host, fmap, matches, n, cap, corr_cap, label, replay=True):
+    """the device and the host build against the reference, every byte; one replay of the device -> (device, reference)"""
+    n_cur = len(fmap["cur_key"])
+    d_fmap = fm.frame_map_to_device(fmap)
+    ref = fr.carry(fmap, matches, n, cap, corr_cap)
+    got = device_carry(fm, d_fmap, matches, n, cap, n_cur, corr_cap)
+    fh.check_carry(got, ref, "device " + label)
+    fh.check_carry(fh.carry(host, fmap, fh.pad_list(matches, cap), n, corr_cap), ref, "host " + label)
+    if replay:
+        again = device_carry(fm, d_fmap, matches, n, cap, n_cur, corr_cap)
+        for k in got:
+            assert got[k].cpu().numpy().tobytes() == again[k].cpu().numpy().tobytes(), (label, k)
+    return got, ref
+
+
+@pytest.mark.parametrize("n_cur,n", EDGE_PAIRS)
+def test_totals_at_the_size_edges(fm, host, n_cur, n):
+    """corr_cap = n_cur + n exactly.  What a size reaches is proven from fr.sorted_words before the device is asked."""
+    fmap, matches = large_scene(n_cur, n)
+    assert (len(fmap["cur_key"]), len(matches)) == (n_cur, n)
+    total, cap = n_cur + n, max(n, 1)
+    words = fr.sorted_words(fmap, matches, n, cap)
+    p2 = 1 << max(total - 1, 0).bit_length()
+    across = [e for e in range(1024, total, 1024) if fr.runs_across(words, e)]
+    print("(%d, %d): total %d, %d valid words, p2 %d, %d chunks of step 3, runs across %s" % (
+        n_cur, n, total, len(words), p2, -(-total // 1024), across))
+    if n_cur == 150:                                     # from index 1023 on padding alone: at 1025 a second chunk runs
+        assert len(words) <= 1023 <= total               # over nothing, and offset must not move
+    if (n_cur, n) in ((3000, 5192), (0, 8192)):
+        assert across and total == p2 == 8192
+    if (n_cur, n) == (8192, 0):
+        assert len(words) == total == p2 == 8192         # no padding: the word at 8191 wins through i + 1 >= n
+    got, ref = carry_three_ways(fm, host, fmap, matches, n, cap, total, "(%d, %d)" % (n_cur, n))
+    assert ref["status"] == 0 and ref["n_map"] == len(set(k for k, _ in words))
+    if (n_cur, n) == (8192, 0):
+        assert ref["n_map"] == 8192 and not got["cur_status"].cpu().numpy().any()
+    if n_cur == 0:
+        assert got["cur_status"].numel() == 0
+
+
+def test_one_over_8192_answers_no_room(fm, host):
+    fmap, matches = large_scene(3000, 5193)
+    _, ref = carry_three_ways(fm, host, fmap, matches, 5193, 5193, 8193, "8193 words", replay=False)
+    assert ref["status"] == -2
+    fmap, matches = large_scene(3000, 5192)
+    _, ref = carry_three_ways(fm, host, fmap, matches, 5192, 5192, 8191, "corr_cap 8191", replay=False)
+    assert ref["status"] == -2
+
+
+def test_boundary_case(fm, host):
+    """runs of equal keys over the chunk edges at 1024 and 3072, a run of one at 2047, on the 64 KiB block"""
+    fmap, matches = fr.boundary_case()
+    runs = fr.boundary_runs(fmap, matches)               # the inputs reach the edges: proven before the device is asked
+    n_cur, n = len(fmap["cur_key"]), len(matches)
+    got, ref = carry_three_ways(fm, host, fmap, matches, n, n, n_cur + n, "boundary")
+    carry_status, cur_status = got["carry_status"].cpu().numpy(), got["cur_status"].cpu().numpy()
+    entry, *three = runs[1022]
+    assert cur_status[entry] == 1 and [carry_status[r - n_cur] for r in sorted(three)] == [4, 4, 0]
+    assert carry_status[runs[2047][0] - n_cur] == 0
+    entry, match = runs[3071]
+    assert cur_status[entry] == 1 and carry_status[match - n_cur] == 0
+    # the records at and behind each edge: a record's place is the number of distinct keys in front of it
+    words = fr.sorted_words(fmap, matches, n, n)
+    keys = sorted(set(k for k, _ in words))
+    rec = got["map"].cpu().numpy()
+    for first, ranks in runs.items():
+        at = keys.index(words[first][0])
+        assert tuple(rec[at][[0, 2]]) == (keys[at], max(ranks) - n_cur), first
+        assert rec[at + 1][0] == keys[at + 1] == words[first + len(ranks)][0], first
+
+
+def test_clipped_long_list(fm, host):
+    fmap, matches = large_scene(3000, 6000)
+    got, ref = carry_three_ways(fm, host, fmap, matches, 6000, 5000, 8000, "n_out 6000, cap 5000")     # the first 5000
+    assert ref["status"] == 0 and tuple(got["carry_status"].shape) == (5000,)
+    assert not (got["carry_status"].cpu().numpy() == 255).any()
+    assert np.array_equal(ref["map"], fr.carry(fmap, matches[:5000], 5000, 5000, 8000)["map"])
 
 
 def test_refusals_write_nothing(fm):

@@ -10,7 +10,7 @@ import pytest
 from tests import frame_tracking_host as fh
 from tests import frame_tracking_ref as fr
 from tests import pose_host
-from tests.test_frame_tracking_ref import dressed
+from tests.test_frame_tracking_ref import dressed, large_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -25,15 +25,22 @@ def pose(tmp_path_factory):
     return pose_host.build(tmp_path_factory.mktemp("pose_host"))
 
 
-@pytest.mark.parametrize("seed", (0, 1, 2))
+def large_case(case):
+    return fr.boundary_case() if case == "boundary" else large_scene()
+
+
+@pytest.mark.parametrize("seed", (0, 1, 2, "boundary", "large"))
 def test_carry_equals_the_reference(host, seed):
-    fmap, matches = fr.scene(seed)
-    for n, cap, corr_cap, min_matches in ((160, 160, 310, 0), (300, 120, 270, 0), (0, 160, 150, 0), (14, 160, 150, 15),
-                                          (160, 160, 309, 0), (-1, 160, 310, 0), (1, 160, 310, 0)):
+    """seeds: 150 entries and a list of 160; boundary and large: more than 4096 words, runs over the chunk edges"""
+    fmap, matches = fr.scene(seed) if isinstance(seed, int) else large_case(seed)
+    n_cur, k = len(fmap["cur_key"]), len(matches)
+    for n, cap, corr_cap, min_matches in ((k, k, n_cur + k, 0), (k + 140, k - 40, n_cur + k - 40, 0), (0, k, n_cur, 0),
+                                          (14, k, n_cur, 15), (k, k, n_cur + k - 1, 0), (-1, k, n_cur + k, 0),
+                                          (1, k, n_cur + k, 0)):
         got = fh.carry(host, fmap, fh.pad_list(matches, cap), n, corr_cap, min_matches)
         fh.check_carry(got, fr.carry(fmap, matches, n, cap, corr_cap, min_matches), (seed, n, cap, corr_cap))
     for what, bad in fr.malformed(fmap):
-        fh.check_carry(fh.carry(host, bad, fh.pad_list(matches, 160), 160, 310), dict(status=-1), what)
+        fh.check_carry(fh.carry(host, bad, fh.pad_list(matches, k), k, n_cur + k), dict(status=-1), what)
 
 
 def test_tied_case(host):
@@ -42,12 +49,15 @@ def test_tied_case(host):
     fh.check_carry(fh.carry(host, fmap, fh.pad_list(matches, n + 3), n, n + 3), fr.carry(fmap, matches, n, n + 3, n + 3), "tied")
 
 
-@pytest.mark.parametrize("kind,seed,observed,n_given", [("base", 1, True, None), ("few", 2, True, None), ("base", 1, False, None),
-                                                        ("wide", 3, True, 14), ("base", 2, True, 9)])
-def test_chain_with_the_pose_host_build(host, pose, kind, seed, observed, n_given):
+@pytest.mark.parametrize("kind,seed,observed,n_given,n_scene", [
+    pytest.param("base", 1, True, None, 96, id="base-1-True-None"), pytest.param("few", 2, True, None, 96, id="few-2-True-None"),
+    pytest.param("base", 1, False, None, 96, id="base-1-False-None"), pytest.param("wide", 3, True, 14, 96, id="wide-3-True-14"),
+    pytest.param("base", 2, True, 9, 96, id="base-2-True-9"), pytest.param("wide", 3, True, None, 1500, id="wide-3-True-None-1500")])
+def test_chain_with_the_pose_host_build(host, pose, kind, seed, observed, n_given, n_scene):
     """carry -> pose_solve.h -> cut, all three as host builds: every integer output equals the reference run on the same
-    outlier bytes, and the list the optimiser was given is the reference's"""
-    fmap, matches, sc = dressed(kind, seed, observed)
+    outlier bytes, and the list the optimiser was given is the reference's.  The scene of 1500: six chunks of the cut,
+    each with kept and removed records."""
+    fmap, matches, sc = dressed(kind, seed, observed, n=n_scene)
     cap = len(matches)
     n = cap if n_given is None else n_given
     min_matches = 15 if n_given != 9 else 0
@@ -69,6 +79,10 @@ def test_chain_with_the_pose_host_build(host, pose, kind, seed, observed, n_give
     assert ref["track_status"] == want
     if want == 0:
         assert ref["n_removed"] > 0 and ref["n_kept"] >= 10
+    if n_scene == 1500:
+        chunks = fr.cut_chunks(outliers[:n_map])
+        print("n_good %d, (kept, removed) per chunk of 256: %s" % (p["n_good"], chunks))
+        assert n_map == 1497 and len(chunks) == 6 and min(min(c) for c in chunks) >= 1
 
 
 def test_edge_inputs_in_a_sanitized_executable(tmp_path):

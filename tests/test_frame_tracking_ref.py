@@ -1,7 +1,8 @@
 """CPU: the two statements of tests/frame_tracking_ref.py -- the sequential code of TrackWithMotionModel /
 TrackReferenceKeyFrame and the order-independent statement of include/msf_frame_tracking.h -- are equal on random scenes
 and on the tied case, the scenes reach every status value, and with pose_ref.pose_optimization behind the carry every
-track_status of a call that runs occurs."""
+track_status of a call that runs occurs.  Both statements also agree at the sizes of a real frame (8192 words; the
+boundary case, whose runs of equal keys lie where the kernel's chunks of 1024 words meet)."""
 import numpy as np
 import pytest
 
@@ -49,6 +50,38 @@ def test_tied_case():
     assert rec[0] == (7, 5) and rec[key(fr.W - 1, fr.H - 1)] == (4, 8) and oi["n_map"] == 8
 
 
+def large_scene():
+    """8192 words, none of them padding: 3000 entries of the frame and a list of 5192"""
+    return fr.scene(7, n_points=3000, n_ref=6000, n_cur=3000, n_matches=5192)
+
+
+def test_boundary_case_lies_on_the_chunk_edges():
+    fmap, matches = fr.boundary_case()
+    runs = fr.boundary_runs(fmap, matches)
+    n_cur, n = len(fmap["cur_key"]), len(matches)
+    c = fr.carry(fmap, matches, n, n, n_cur + n)
+    assert (c["carry_status"] == 1).sum() == 7 and (c["carry_status"] == 3).sum() == 9
+    assert len(fr.sorted_words(fmap, matches, n, n)) == fr.BOUNDARY_WORDS == n_cur + n - 16
+    entry, *three = runs[1022]
+    assert c["cur_status"][entry] == 1 and sorted(c["carry_status"][r - n_cur] for r in three) == [0, 4, 4]
+    assert c["carry_status"][max(three) - n_cur] == 0                       # the largest j wins
+    assert c["carry_status"][runs[2047][0] - n_cur] == 0
+    entry, match = runs[3071]
+    assert c["cur_status"][entry] == 1 and c["carry_status"][match - n_cur] == 0
+    ranks = np.array([r for _, r in fr.sorted_words(fmap, matches, n, n) if r >= n_cur])
+    assert (np.diff(ranks) < 0).sum() > len(ranks) // 3                     # shuffled: rank order is not key order
+
+
+@pytest.mark.parametrize("case", ("boundary", "large"))
+def test_literal_equals_order_independent_past_one_chunk(case):
+    fmap, matches = fr.boundary_case() if case == "boundary" else large_scene()
+    n, n_cur = len(matches), len(fmap["cur_key"])
+    if case == "large":
+        assert (n_cur, n) == (3000, 5192)
+    for opt in (fr.no_optimiser, flag_some(0.3, 7)):
+        fr.agree(fr.literal(fmap, matches, n, n, 15, 10, opt), fr.order_independent(fmap, matches, n, n, n_cur + n, 15, 10, opt))
+
+
 def test_refused_inputs():
     fmap, matches = fr.scene(0)
     assert fr.carry(fmap, matches, -1, 160, 400)["status"] == -3
@@ -60,13 +93,14 @@ def test_refused_inputs():
         assert fr.carry(m, matches, 160, 160, 400)["status"] == -1, what
 
 
-def dressed(kind, seed, observed=True, repeat=4, blind=5):
-    """A pose_ref scene as a train map plus a match list: correspondence i is match i from the pixel of p2d to a train
-    pixel of its own that holds point i; `repeat` more matches repeat an earlier k1 with another point and `blind` carry
-    no point.  -> (fmap, matches, sc)"""
+def dressed(kind, seed, observed=True, repeat=4, blind=5, n=pose_ref.N_SCENE):
+    """A pose_ref scene of n correspondences as a train map plus a match list: correspondence i is match i from the pixel
+    of p2d to a train pixel of its own that holds point i; `repeat` more matches repeat an earlier k1 with another point
+    and `blind` carry no point.  observed: True (no table: every point counts), False (none does) or a uint8 [n] table.
+    -> (fmap, matches, sc)"""
     from tests import tracking_ref as tr
-    sc = pose_ref.scene(kind, seed)
-    n = len(sc["p3d"])
+    sc = pose_ref.scene(kind, seed, n)
+    assert n == len(sc["p3d"])
     rng = np.random.default_rng(seed)
     pts = np.zeros(n, tr.MAP_POINT)
     pts["pos"] = sc["p3d"]
@@ -76,8 +110,12 @@ def dressed(kind, seed, observed=True, repeat=4, blind=5):
         rows.insert(3 * r, (rows[-1 - r][0], rows[-1 - r][1], rows[r][2], rows[r][3]))    # overwritten by the later match
     for b in range(blind):
         rows.append((10 + b, 10, 3 + b, 1) if (1 * fr.W + 3 + b) not in set(ref_key) else (10 + b, 10, -1, 1))
+    if isinstance(observed, np.ndarray):
+        assert observed.dtype == np.uint8 and observed.shape == (n,)
+    else:
+        observed = None if observed else np.zeros(n, np.uint8)
     fmap = dict(points=pts, ref_key=ref_key, ref_point=np.arange(n, dtype=np.int32), cur_key=np.zeros(0, np.int32),
-                cur_point=np.zeros(0, np.int32), observed=None if observed else np.zeros(n, np.uint8))
+                cur_point=np.zeros(0, np.int32), observed=observed)
     return fmap, np.array(rows, np.int32), sc
 
 

@@ -12,7 +12,7 @@ from tests import pose_ref as pr
 
 pytestmark = pytest.mark.gpu
 
-SIZES = [0, 2, 3, 9, 10, 63, 64, 65, 128, 129, 257]
+SIZES = [0, 2, 3, 9, 10, 63, 64, 65, 128, 129, 257, 1025, 4097, 8192]    # the last three: 17, 65 and 128 strides of a lane
 SENTINEL = {"uint8": 0xAB, "int32": -77, "float32": -77.0, "float64": -77.0}
 
 

@@ -4,7 +4,8 @@ which a few matches repeat a k1 and a few carry no point.  Every integer output 
 on the device's own outlier bytes; Tcw, n_good, outliers and pose_f64 equal msf_pose_optimize on the host-gathered,
 key-ordered list BIT FOR BIT (the equality include/msf_pose.h already promises of its device form: no tolerance here);
 the kept map is a current-frame map that msf_claim_points_device accepts.  The gate on both sides of min_matches, n_map
-of 2 / 3 / 9 / 10, an invalid list, and track_status 2 with nothing observed."""
+of 2 / 3 / 9 / 10, an invalid list, and track_status 2 with nothing observed.  Past one chunk of the cut: n_map on both
+sides of 256, 512 and 1024, scenes of 1500 and 3000 correspondences, and a gated call on a frame map of 600 entries."""
 import numpy as np
 import pytest
 
@@ -134,6 +135,78 @@ def test_short_maps(fm, n_map):
     assert len(set((int(a), int(b)) for a, b in m[:, :2])) == n_map
     got, ref = check(fm, fmap, m, n_map, sc, "n_map %d" % n_map, min_matches=0, min_map_matches=2)
     assert ref["n_map"] == n_map and ref["track_status"] == 0
+
+
+# ---- past one chunk of the cut: maps of more than 256 records, lanes of the optimiser with up to 47 strides --------------
+
+CUT_SIZES = (256, 257, 512, 513, 1024, 1025)
+_LONG = {}
+
+
+def observed_mask(n, seed=11):
+    return (np.random.default_rng(seed).random(n) < 0.8).astype(np.uint8)
+
+
+def long_scene():
+    """("base", 2) with 1100 correspondences, no match repeated or blind, 80 % of the points observed; computed once"""
+    if not _LONG:
+        _LONG["scene"] = dressed("base", 2, n=1100, repeat=0, blind=0, observed=observed_mask(1100))
+    return _LONG["scene"]
+
+
+def window(matches, sc, n_map):
+    """Rows of the list (row i is correspondence i) with pairwise distinct (x1, y1), so that the map has exactly n_map
+    records: n_map of them that are consecutive in key order and end at an outlier of the scene.  The one record of
+    the last chunk of 257 / 513 / 1025 is then one the optimiser flags."""
+    key = matches[:, 1] * fr.W + matches[:, 0]
+    _, first = np.unique(key, return_index=True)                  # one row per pixel, in key order
+    last = max(i for i in np.flatnonzero(sc["outlier"][first]) if i >= n_map - 1)
+    return np.sort(first[last - n_map + 1:last + 1])
+
+
+def check_chunks(ref, label):
+    """No pass on an empty case: on the device's own outlier bytes every chunk of 256 records of the map holds a removed
+    and a kept record -- but a last chunk of one record, which can hold one of the two and holds a removed one --, some
+    kept points are not observed, and the frame is tracked."""
+    chunks = fr.cut_chunks(ref["outliers"])
+    print("%s: n_map %d, (kept, removed) per chunk of the cut %s, n_matches_map %d of %d kept" % (
+        label, ref["n_map"], chunks, ref["n_matches_map"], ref["n_kept"]))
+    assert len(chunks) == -(-ref["n_map"] // 256) >= 1, label
+    for kept, removed in chunks:
+        assert removed >= 1 and (kept >= 1 or kept + removed == 1), (label, chunks)
+    assert ref["n_matches_map"] < ref["n_kept"] and ref["track_status"] == 0, label
+
+
+@pytest.mark.parametrize("n_map", CUT_SIZES)
+def test_maps_at_the_chunk_edges_of_the_cut(fm, n_map):
+    fmap, matches, sc = long_scene()
+    m = matches[window(matches, sc, n_map)]
+    assert len(set((int(a), int(b)) for a, b in m[:, :2])) == len(m) == n_map
+    got, ref = check(fm, fmap, m, n_map, sc, "n_map %d" % n_map)
+    assert ref["n_map"] == n_map
+    check_chunks(ref, "n_map %d" % n_map)
+
+
+@pytest.mark.parametrize("kind,seed,n,n_map", [("wide", 3, 1500, 1497), ("base", 2, 3000, 2982)])
+def test_scenes_of_thousands(fm, kind, seed, n, n_map):
+    """6 and 12 chunks of the cut behind a carry of two chunks / three chunks of step 3"""
+    fmap, matches, sc = dressed(kind, seed, n=n, observed=observed_mask(n))
+    label = "%s %d n %d" % (kind, seed, n)
+    got, ref = check(fm, fmap, matches, len(matches), sc, label)
+    print("%s: n_good %d" % (label, int(got["n_good"][0])))
+    assert ref["n_map"] == n_map and (ref["carry_status"] == 4).sum() >= 4 and (ref["carry_status"] == 3).sum() >= 5
+    check_chunks(ref, label)
+
+
+def test_gated_call_keeps_a_frame_map_of_three_chunks(fm):
+    fmap, matches, sc = dressed("base", 3)
+    rng = np.random.default_rng(6)
+    own = np.sort(rng.choice(fr.W * fr.H, 600, replace=False)).astype(np.int32)
+    fmap = dict(fmap, cur_key=own, cur_point=rng.integers(0, len(fmap["points"]), 600).astype(np.int32))
+    got, ref = check(fm, fmap, matches, 14, sc, "n = min_matches - 1, 600 entries")
+    assert ref["track_status"] == 1 and ref["n_map"] == ref["n_kept"] == 600 and ref["n_removed"] == 0
+    assert np.array_equal(got["kept_key"][:600], own) and np.array_equal(got["kept_point"][:600], fmap["cur_point"])
+    assert (got["map"][:600, 3] == 0).all() and got["Tcw"][0].tobytes() == np.asarray(sc["Tcw0"], np.float32).tobytes()
 
 
 def test_nothing_observed_is_status_2(fm):
