@@ -9,7 +9,9 @@ LIB = os.path.join(_HERE, "libmsf.so")
 SYNTH = os.path.join(_HERE, "libmsf_synth.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-HIP_SOURCES = ["msf_abi.cpp", "msf_multi.cpp", "msf_gather.cpp", "weights_io.cpp", "orb_kernels.hip", "loftr_kernels.hip", "pack_kernels.hip",
+HIP_SOURCES = ["msf_abi.cpp", "abi_initializer.cpp", "abi_local_mapping.cpp", "abi_pnp.cpp", "abi_pose.cpp", "abi_ba.cpp",
+               "abi_tracking.cpp", "abi_frame_tracking.cpp",
+               "msf_multi.cpp", "msf_gather.cpp", "weights_io.cpp", "orb_kernels.hip", "loftr_kernels.hip", "pack_kernels.hip",
                "ransac_kernels.hip", "reconstruct_kernels.hip", "triangulate_kernels.hip", "pnp_kernels.hip", "pose_kernels.hip",
                "ba_kernels.hip", "gba_kernels.hip", "tracking_kernels.hip", "frame_tracking_kernels.hip"]
 # -ffp-contract=off + correctly rounded f32 divide: the few f32 steps inside ORB
@@ -30,15 +32,8 @@ def _stale(target, deps):
 
 def _deps():
     d = [os.path.join(CSRC, f) for f in os.listdir(CSRC)]
-    d.append(os.path.join(ROOT, "include", "msf_abi.h"))
-    d.append(os.path.join(ROOT, "include", "msf_initializer.h"))
-    d.append(os.path.join(ROOT, "include", "msf_local_mapping.h"))
-    d.append(os.path.join(ROOT, "include", "msf_pnp.h"))
-    d.append(os.path.join(ROOT, "include", "msf_pose.h"))
-    d.append(os.path.join(ROOT, "include", "msf_ba.h"))
-    d.append(os.path.join(ROOT, "include", "msf_global_ba.h"))
-    d.append(os.path.join(ROOT, "include", "msf_tracking.h"))
-    d.append(os.path.join(ROOT, "include", "msf_frame_tracking.h"))
+    inc = os.path.join(ROOT, "include")
+    d += [os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")]
     return d
 
 

@@ -58,6 +58,15 @@ def test_no_cpu_fallback():
         DNNFeatureMatcher()
 
 
+def test_every_source_is_built():
+    """build_lib() and build_variant() leave out a listed source that does not exist, and a file that is not listed is
+    never compiled: HIP_SOURCES is exactly the *.cpp and *.hip of csrc/ (synth.c goes into a library of its own)."""
+    from mono_slam_framework_amd import build
+    on_disk = sorted(f for f in os.listdir(build.CSRC) if f.endswith((".cpp", ".hip")))
+    assert len(set(build.HIP_SOURCES)) == len(build.HIP_SOURCES)
+    assert sorted(build.HIP_SOURCES) == on_disk
+
+
 def test_product_does_not_reference_oracle():
     pkg = os.path.join(ROOT, "mono_slam_framework_amd")
     for dp, _, fs in os.walk(pkg):

@@ -1,4 +1,4 @@
-"""GPU: the contract of the extern "C" boundary itself (csrc/msf_abi.cpp), entry point by entry point: what a null
+"""GPU: the contract of the extern "C" boundary itself (csrc/msf_abi.cpp, csrc/abi_*.cpp), entry point by entry point: what a null
 handle and a bad argument return and leave in msf_last_error, that a handle works after a refused call, the chunked
 host batch, the count-only one-to-many call, and the grow-on-demand workspaces.  Codes and texts are the ones
 include/msf_abi.h documents and the library has always produced; nothing here looks at a kernel's numbers beyond

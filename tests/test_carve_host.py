@@ -1,4 +1,4 @@
-"""CPU: csrc/carve.h -- the carver behind every geometry workspace of msf_abi.cpp -- in a stand-alone sanitized
+"""CPU: csrc/carve.h -- the carver behind every geometry workspace of abi_*.cpp -- in a stand-alone sanitized
 executable (tests/cpp/carve_main.cpp), never inside python.  The measuring pass sizes a malloc block of exactly the bytes
 it reports and the placing pass writes every piece of it in full: a piece that the first pass did not count is an
 overrun that AddressSanitizer reports here, where on the device it would be a write past the workspace."""

@@ -1,4 +1,4 @@
-"""The contract of include/msf_initializer.h (msf_reconstruct, msf_reconstruct_device; bodies in csrc/msf_abi.cpp), as
+"""The contract of include/msf_initializer.h (msf_reconstruct, msf_reconstruct_device; bodies in csrc/abi_initializer.cpp), as
 test_abi_contract_gpu.py keeps it for msf_abi.h: the header is plain C99, every name it declares is exported and bound,
 the ctypes structs have the C sizes (CPU part, not marked gpu); a null handle, every refusal with its text, and a good
 call after each refusal (GPU part).  The entry points of msf_initializer.h are listed here and in
