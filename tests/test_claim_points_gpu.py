@@ -1,7 +1,8 @@
 """GPU: msf_claim_points_device (steps 4-5 of include/msf_tracking.h) on injected lists -- extracted frames never give the
 tied and edge cases.  The records, statuses, n_claimed and corr_* are exactly those of tests/tracking_ref.py's
 order-independent statement (which test_tracking_ref.py proves equal to the literal sequential loop) and of the host
-build of csrc/tracking_solve.h."""
+build of csrc/tracking_solve.h.  The last tests repeat this with lists, runs, key frames and the frame's own map past one
+chunk of 256 (tracking_ref.CHUNK_CASES)."""
 import numpy as np
 import pytest
 
@@ -42,8 +43,10 @@ def run_device(fm, lmap, lists, n_out, matched, cap, corr_cap):
     return got
 
 
-def check(fm, host, lmap, prm, lists, n_out, cap, corr_cap, matched=None, label=""):
-    ref = tr.order_independent(lmap, prm, lists, n_out, cap, corr_cap, matched=matched)
+def check(fm, host, lmap, prm, lists, n_out, cap, corr_cap, matched=None, label="", ref=None):
+    """ref: order_independent() of these very arguments where the caller has it already"""
+    if ref is None:
+        ref = tr.order_independent(lmap, prm, lists, n_out, cap, corr_cap, matched=matched)
     got = run_device(fm, lmap, lists, n_out, ref["matched"], cap, corr_cap)
     assert int(got["status_word"][0]) == 0
     th.check_claims(got, ref, n_out, cap, label)
@@ -115,3 +118,35 @@ def test_a_malformed_map_writes_only_status_word_and_zero_key_frames_are_no_erro
     got = run_device(fm, none, [], np.zeros(0, np.int32), np.zeros(0, np.uint8), 32, 200)
     assert int(got["status_word"][0]) == 0 and got["n_claims"] == 0 and got["n_corr"][0] == 8
     assert np.array_equal(got["corr_point"][:8], lmap["cur_point"])
+
+
+# ---- past one chunk of 256 (tracking_ref.CHUNK_CASES; test_tracking_ref.py asserts what each case reaches) ---------------
+
+@pytest.mark.parametrize("name", list(tr.CHUNK_CASES))
+def test_lists_runs_and_key_frames_past_one_chunk(fm, host, name):
+    """k_claim_mark at blockIdx.x >= 2, k_claim_pack's running offset over three and more chunks with winners and
+    losers of one pixel in different chunks and key frames, k_claim_finish's k += 256 sums and its row n_kf at
+    blockIdx.x > 0 -- once behind the gate of step 3, once with every key frame matched"""
+    lmap, prm, lists, n_out, cap = tr.chunk_case(name)
+    corr_cap = tr.corr_room(lmap, lists, cap)
+    for forced in (False, True):
+        ref = tr.chunk_reference(name, forced)
+        _, got = check(fm, host, lmap, prm, lists, n_out, cap, corr_cap, label="%s forced %d" % (name, forced), ref=ref)
+        k = ref["n_corr"]
+        assert k == len(lmap["cur_key"]) + ref["n_claims"]
+        assert not got["corr_point"][k:].any() and not got["corr_p2d"][k:].any() and not got["corr_p3d"][k:].any()
+        if forced and name in ("long", "ladder-320-empty"):      # the call is bit-identical to a second call
+            again = run_device(fm, lmap, lists, n_out, ref["matched"], cap, corr_cap)
+            for key in got:
+                assert np.asarray(got[key]).tobytes() == np.asarray(again[key]).tobytes(), key
+
+
+def test_a_map_malformed_past_the_first_chunk_writes_only_status_word(fm):
+    lmap, prm, lists, n_out, cap = tr.chunk_case("long")
+    for key, at, value in tr.late_faults(lmap):
+        got = run_device(fm, tr.with_fault(lmap, key, at, value), lists, n_out, np.ones(4, np.uint8), cap,
+                         tr.corr_room(lmap, lists, cap))
+        assert int(got["status_word"][0]) == -1 and got["n_claims"] == 0 and not got["n_claimed"].any(), (key, at)
+        assert (got["claims"] == -9).all() and (got["claim_status"] == 255).all(), (key, at)
+        assert not got["corr_point"].any() and not got["corr_p3d"].any() and not got["corr_p2d"].any(), (key, at)
+        assert int(got["n_corr"][0]) == 0, (key, at)

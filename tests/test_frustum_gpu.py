@@ -2,7 +2,8 @@
 status, owner_kf, n_to_match and the diagnostics equal the host build of csrc/tracking_solve.h bit for bit (square root
 and division are correctly rounded on both sides, contraction is off), equal the float64 reference outside the threshold
 bands, the device entry equals the host entry, a malformed device call writes only status_word, and the bytes beyond
-every array stay untouched."""
+every array stay untouched.  The last tests repeat this past one chunk of 256 in every dimension of the checking kernel,
+of k_frustum and of k_gate (tracking_ref.CHUNK_CASES)."""
 import numpy as np
 import pytest
 
@@ -140,6 +141,47 @@ def test_a_malformed_device_call_writes_only_status_word(fm):
     out, _ = guarded_out(70, 3)
     fm.frustum_device(fm.local_map_to_device(lmap), tr.view_of(prm), prm["Ow"], tr.bounds_of(prm), 0.5, out=out)
     assert int(out["status_word"].cpu()[0]) == 0
+
+
+# ---- past one chunk of 256 (tracking_ref.CHUNK_CASES; test_tracking_ref.py asserts what each case reaches) ---------------
+
+DISTINCT_MAPS = [k for k in tr.CHUNK_CASES if "-cap" not in k]      # the clipped cases share the long-runs map
+
+
+def device_bytes(fm, lmap, prm):
+    out, full = guarded_out(len(lmap["points"]), max(len(lmap["kf_start"]) - 1, 0))
+    fm.frustum_device(fm.local_map_to_device(lmap), tr.view_of(prm), prm["Ow"], tr.bounds_of(prm), float(prm["cos_limit"]), out=out)
+    return {k: full[k].cpu().numpy().tobytes() for k in NAMES + ("status_word",)}
+
+
+@pytest.mark.parametrize("name", DISTINCT_MAPS)
+def test_runs_key_frames_and_the_frames_map_past_one_chunk(fm, host, name):
+    """k_track_check's e += 256 loop and its second and third block ranges past one workgroup, the owner word met
+    from several chunks and key frames, kf_of_entry over a long kf_start with repeated values, 64 distinct key frames
+    in one wave of k_frustum, k_gate's i += 256"""
+    lmap, prm, _, _, _ = tr.chunk_case(name)
+    worst, in_band = run_all(fm, host, lmap, prm, name)
+    print("device %s: worst fraction of a bar %.3f, %.2f %% in a band" % (name, worst, 100 * in_band))
+    ref = tr.chunk_reference(name)
+    got = fm.frustum(lmap, tr.view_of(prm), prm["Ow"], tr.bounds_of(prm), float(prm["cos_limit"]))
+    for k in ("status", "visible", "owner_kf", "n_to_match"):
+        assert np.array_equal(got[k], ref[k]), k
+    if name in ("long", "ladder-320-empty"):      # the call is bit-identical to a second call, guard bytes included
+        first, again = device_bytes(fm, lmap, prm), device_bytes(fm, lmap, prm)
+        for k in first:
+            assert first[k] == again[k], k
+
+
+def test_a_map_malformed_past_the_first_chunk_writes_only_status_word(fm):
+    lmap, prm, _, _, _ = tr.chunk_case("long")
+    n_points, n_kf = len(lmap["points"]), len(lmap["kf_start"]) - 1
+    for key, at, value in tr.late_faults(lmap):
+        out, full = guarded_out(n_points, n_kf)
+        fm.frustum_device(fm.local_map_to_device(tr.with_fault(lmap, key, at, value)), tr.view_of(prm), prm["Ow"],
+                          tr.bounds_of(prm), 0.5, out=out)
+        assert int(out["status_word"].cpu()[0]) == -1, (key, at)
+        for k in NAMES:
+            assert untouched(full[k], 0), (key, at, k)
 
 
 def test_host_entry_refusals(fm):

@@ -20,32 +20,53 @@ CAP = 2048
 GATED = 2          # the key frame whose points all lie behind the camera
 
 
-def local_map_from_lists(lists, prm, seed=0):
+def local_map_from_lists(lists, prm, seed=0, pad=0):
     """A local map whose key frames hold a point under the train end of every second match and whose frame holds one
     under the query end of every fifth, so that the extracted lists give claims, occupied pixels and misses.  The points
     of key frame GATED lie behind the camera; all others in front of it, seen head-on, where the frame sees the query
-    end of their match: a claim is a consistent correspondence for the pose, the frame's own entries are not."""
+    end of their match: a claim is a consistent correspondence for the pose, the frame's own entries are not.
+    pad: so many more points in every key frame, under train keys that no match of its list ends at (visible, but
+    behind the camera in key frame GATED: the gate stays shut), and so many more entries of the frame's own map under
+    keys that no match of any list starts at, each with a point of its own that projects there.  With pad = 0 nothing
+    is drawn for them."""
     rng = np.random.default_rng(seed)
     R, t = prm["Rcw"].reshape(3, 3).astype(np.float64), prm["tcw"].astype(np.float64)
     pts, kf_start, kf_key, kf_point, cur = [], [0], [], [], {}
+
+    def add_point(px, py, z):
+        pc = np.array([(px - 320) / 500 * abs(z), (py - 240) / 500 * abs(z), z])
+        pos = (R.T @ (pc - t)).astype(np.float32)
+        po = pos.astype(np.float64) - prm["Ow"].astype(np.float64)
+        p = np.zeros((), tr.MAP_POINT)
+        p["pos"], p["normal"], p["max_distance"] = pos, po / np.linalg.norm(po), 100.0
+        pts.append(p)
+        return len(pts) - 1
     for i, l in enumerate(lists):
         seen_at = {}     # train key -> the query end of the first match that has it: the point projects there
         for (x1, y1, x2, y2) in l[::2]:
             seen_at.setdefault(int(y2) * W + int(x2), (int(x1), int(y1)))
+        entries = []
         for k in sorted(seen_at):
             z = -4.0 if i == GATED else rng.uniform(2, 8)
             px, py = seen_at[k]
-            pc = np.array([(px - 320) / 500 * abs(z), (py - 240) / 500 * abs(z), z])
-            pos = (R.T @ (pc - t)).astype(np.float32)
-            po = pos.astype(np.float64) - prm["Ow"].astype(np.float64)
-            p = np.zeros((), tr.MAP_POINT)
-            p["pos"], p["normal"], p["max_distance"] = pos, po / np.linalg.norm(po), 100.0
+            entries.append((k, add_point(px, py, z)))
+        last = len(pts) - 1 if pts else 0
+        if pad:
+            free = np.setdiff1d(np.arange(W * H), [int(y2) * W + int(x2) for (_, _, x2, y2) in l])
+            for k in rng.choice(free, pad, replace=False):
+                z = -4.0 if i == GATED else rng.uniform(2, 8)
+                entries.append((int(k), add_point(rng.uniform(20, W - 20), rng.uniform(20, H - 20), z)))
+        for k, p in sorted(entries):
             kf_key.append(k)
-            kf_point.append(len(pts))
-            pts.append(p)
+            kf_point.append(p)
         kf_start.append(len(kf_key))
         for (x1, y1, _, _) in l[::5]:
-            cur.setdefault(int(y1) * W + int(x1), len(pts) - 1 if pts else 0)
+            cur.setdefault(int(y1) * W + int(x1), last)
+    if pad:
+        starts = [int(y1) * W + int(x1) for l in lists for (x1, y1, _, _) in l]
+        free = np.setdiff1d(np.arange(W * H), starts + list(cur))
+        for k in rng.choice(free, pad, replace=False):
+            cur[int(k)] = add_point(int(k) % W, int(k) // W, rng.uniform(2, 8))
     pts = np.array(pts, tr.MAP_POINT)
     cur_key = np.array(sorted(cur), np.int32)
     cur_point = np.array([cur[k] for k in sorted(cur)], np.int32)
@@ -54,7 +75,7 @@ def local_map_from_lists(lists, prm, seed=0):
                 kf_point=np.array(kf_point, np.int32), cur_key=cur_key, cur_point=cur_point)
 
 
-def check_search(fm, frames, label, need_claims):
+def check_search(fm, frames, label, need_claims, pad=0):
     import torch
     from mono_slam_framework_amd import _lib
     for i, f in enumerate(frames):
@@ -64,7 +85,9 @@ def check_search(fm, frames, label, need_claims):
     num0, _, lists0 = fm.match_one_to_many(0, slots, cap=CAP)
     assert (num0 >= 0).all() and num0[GATED] > 0, num0     # the gate has a list to withhold
     prm = tr.camera(1)
-    lmap = local_map_from_lists(lists0, prm)
+    lmap = local_map_from_lists(lists0, prm, pad=pad)
+    if pad:      # every run and the frame's own map pass one chunk of 256
+        assert np.diff(lmap["kf_start"]).min() > 256 and len(lmap["cur_key"]) > 256
     args = (tr.view_of(prm), prm["Ow"], tr.bounds_of(prm), 0.5)
     got = fm.search_local_points(0, slots, lmap, *args, cap=CAP)
     fr = got["frustum"]
@@ -141,6 +164,13 @@ def orb_frames():
 
 def test_orb_search_local_points(orb, orb_frames):
     check_search(orb, orb_frames, "orb", need_claims=True)
+
+
+def test_orb_search_local_points_past_one_chunk(orb, orb_frames):
+    """the fused call with every key frame's run and the frame's own map longer than 256: the checking kernel's loop
+    and third block range, the claims' lookups in long runs, the correspondences of the frame's map from more than
+    one workgroup -- behind the same comparisons"""
+    check_search(orb, orb_frames, "orb padded", need_claims=True, pad=300)
 
 
 def test_loftr_search_local_points():

@@ -3,7 +3,8 @@
 within the bars written out there and bit for bit against its numpy float32 restatement, steps 1, 4 and 5 exactly
 against the order-independent statement.  The device build runs the same expressions in the same order; what only the
 GPU can show is in test_frustum_gpu.py and test_claim_points_gpu.py.  The empty, one-element and malformed inputs run in
-a stand-alone sanitized executable, never inside python."""
+a stand-alone sanitized executable, never inside python.  The scenes past one chunk of 256 (tracking_ref.CHUNK_CASES) and
+the maps that are malformed only there are held to the same references."""
 import os
 import subprocess
 
@@ -72,6 +73,34 @@ def test_malformed_maps_are_refused(host):
     assert th.frustum(host, bad, prm)["status_word"] == -1
     nan = dict(prm, max_x=np.float32(np.nan))
     assert th.frustum(host, lmap, nan)["status_word"] == -1
+
+
+@pytest.mark.parametrize("name", list(tr.CHUNK_CASES))
+def test_host_build_equals_the_reference_past_one_chunk(host, name):
+    """runs, key frames, the frame's map and lists past 256 (tracking_ref.CHUNK_CASES): steps 1-2 and, once with the
+    gate of step 3 and once with every key frame matched, steps 4-5"""
+    lmap, prm, lists, n_out, cap = tr.chunk_case(name)
+    ref = tr.chunk_reference(name)
+    got = th.frustum(host, lmap, prm)
+    assert got["status_word"] == 0
+    diag = np.stack([got[k] for k in ("u", "v", "dist", "view_cos")], 1)
+    for k in ("status", "visible", "owner_kf", "n_to_match"):
+        assert np.array_equal(got[k], ref[k]), k
+    assert np.array_equal(diag.view(np.uint32), ref["diag"].view(np.uint32))
+    tr.check_against_f64(lmap["points"], prm, got["status"], diag, got["status"] >= 7, "host " + name)
+    padded = th.pad_lists(lists, cap)
+    for forced in (False, True):
+        ref = tr.chunk_reference(name, forced)
+        claimed = th.claims(host, lmap, padded, n_out, ref["matched"], tr.corr_room(lmap, lists, cap))
+        th.check_claims(claimed, ref, n_out, cap, "host %s forced %d" % (name, forced))
+
+
+def test_late_malformed_maps_are_refused(host):
+    """the faults that only a later chunk or workgroup of the checking kernel meets"""
+    lmap, prm, _, _, _ = tr.chunk_case("long")
+    assert th.frustum(host, lmap, prm)["status_word"] == 0
+    for key, at, value in tr.late_faults(lmap):
+        assert th.frustum(host, tr.with_fault(lmap, key, at, value), prm)["status_word"] == -1, (key, at)
 
 
 def test_edge_inputs_in_a_sanitized_executable(tmp_path):

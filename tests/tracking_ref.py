@@ -289,11 +289,14 @@ def bounds_of(prm):
     return (float(prm["min_x"]), float(prm["max_x"]), float(prm["min_y"]), float(prm["max_y"]))
 
 
-def scene(seed, n_points=900, n_kf=8, per_kf=200, n_cur=150, list_len=160, empty_kf=None):
+def scene(seed, n_points=900, n_kf=8, per_kf=200, n_cur=150, list_len=160, empty_kf=None, kf_sizes=None):
     """A local map and match lists that reach every frustum code and every claim status: the camera looks at a slab of
     depths 2..8; of the points some lie behind the camera, outside each image edge, beyond max_distance, are seen at
-    more than 60 degrees, are bad, seen, not finite or referred to by no entry.
+    more than 60 degrees, are bad, seen, not finite or referred to by no entry.  kf_sizes [n_kf]: the exact entry count
+    of every key frame in place of per_kf +- 10 (no draw is made for a size then; without it every draw is what it was,
+    which test_tracking_ref.py pins).
     -> (lmap dict as matcher.make_local_map gives it, prm, lists [n_kf] int32 [k, 4], n_out int32 [n_kf])"""
+    assert kf_sizes is None or len(kf_sizes) == n_kf
     rng = np.random.default_rng(seed)
     prm = camera(seed)
     R, t = prm["Rcw"].reshape(3, 3).astype(np.float64), prm["tcw"].astype(np.float64)
@@ -333,7 +336,10 @@ def scene(seed, n_points=900, n_kf=8, per_kf=200, n_cur=150, list_len=160, empty
     cur_key = np.sort(rng.choice(W * H, len(cur_point), replace=False)).astype(np.int32)
     kf_start, kf_key, kf_point = [0], [], []
     for i in range(n_kf):
-        m = 0 if i == empty_kf or not len(referred) else per_kf + int(rng.integers(-10, 10))
+        if kf_sizes is not None:
+            m = int(kf_sizes[i]) if len(referred) else 0
+        else:
+            m = 0 if i == empty_kf or not len(referred) else per_kf + int(rng.integers(-10, 10))
         kf_key.append(np.sort(rng.choice(W * H, m, replace=False)))
         kp = rng.choice(referred, m) if m else np.zeros(0, np.int64)
         if m > 4:
@@ -404,3 +410,155 @@ def tied_case():
              np.array([(90, 90, 8, 8)], np.int32)]                            # invalid: n_out = -1
     n_out = np.array([len(lists[0]), 2, 4, 4, -1], np.int32)
     return lmap, prm, lists, n_out
+
+
+# ---- scenes past one chunk of 256 -----------------------------------------------------------------------------------------
+# tracking_kernels.hip works in chunks of 256 threads: the entries of a key frame, the key frames, the frame's own map and
+# the matches of a list each have code that only runs past the first chunk.  The cases below reach it; the CPU tests
+# hold literal(), order_independent() and the host build to each other on them and assert that they do reach it, the
+# GPU tests hold the device to the same references.
+
+def ladder_empty_runs(n_kf, n_empty_runs):
+    """-> [(first, length)] of the ladder's stretches of empty key frames: the first at the very end, the second across
+    index 256 (in the middle of a shorter ladder), the third in the first quarter"""
+    assert 0 <= n_empty_runs <= 3 and (n_empty_runs == 0 or n_kf >= 32)
+    runs = [(n_kf - 3, 3), (254, 5) if n_kf >= 270 else (n_kf // 2, 5), (n_kf // 4, 2)]
+    return runs[:n_empty_runs]
+
+
+def ladder(n_kf, rounds, n_empty_runs=0):
+    """Deterministic.  Of the L non-empty key frames the q-th owns the points q, q + L, q + 2 L, ..: point p is owned by
+    non-empty key frame p % L at entry p // L of its run, so with L >= 64 every aligned group of 64 points has 64
+    owners.  Every point lies in front of the camera, projects inside the image, is seen head-on and has a large
+    max_distance: status 0, n_to_match == rounds.  Every key frame but the first also refers, last in its run, to the
+    first point of the one before it, which that one keeps.  The stretches of empty key frames (ladder_empty_runs)
+    repeat values in kf_start.  The lists hold 4..6 matches: k1 shared by key frames i and i + 256 (the lower wins) and
+    repeated inside the list, a free k1, one outside the image, an occupied one, a k2 without an entry.
+    -> (lmap, prm, lists, n_out) as scene() gives them"""
+    prm = camera(0)
+    R, t = prm["Rcw"].reshape(3, 3).astype(np.float64), prm["tcw"].astype(np.float64)
+    empty = np.zeros(n_kf, bool)
+    for a, k in ladder_empty_runs(n_kf, n_empty_runs):
+        empty[a:a + k] = True
+    live = np.flatnonzero(~empty)
+    L = len(live)
+    n_points = L * rounds
+    p = np.arange(n_points)
+    z = 2.0 + p % 7
+    pc = np.stack([(20 + (37 * p) % 601 - 320) / 500 * z, (20 + (53 * p) % 441 - 240) / 500 * z, z], 1)
+    pts = np.zeros(n_points, MAP_POINT)
+    pts["pos"] = ((pc - t) @ R).astype(np.float32)                 # R' (pc - t)
+    po = pts["pos"].astype(np.float64) - prm["Ow"].astype(np.float64)
+    pts["normal"] = po / np.linalg.norm(po, axis=1, keepdims=True)
+    pts["max_distance"] = 100.0
+    key_of = lambda q, r: 5000 * r + 7 * q                          # strictly increasing in r: 7 q < 5000
+    cur_key = (300000 + 11 * np.arange(8)).astype(np.int32)
+    cur_point = (np.arange(8) % n_points).astype(np.int32)
+    kf_start, kf_key, kf_point, lists = [0], [], [], []
+    for i in range(n_kf):
+        q = int(np.searchsorted(live, i))
+        if not empty[i]:
+            kf_key += [key_of(q, r) for r in range(rounds)]
+            kf_point += [q + r * L for r in range(rounds)]
+            if q > 0:
+                kf_key.append(key_of(q, rounds))
+                kf_point.append(q - 1)
+        kf_start.append(len(kf_key))
+        shared, occupied = 100000 + i % 256, int(cur_key[i % 8])
+        k2 = [key_of(q, 0), key_of(q, rounds - 1), key_of(q, 0), key_of(q, 0), key_of(q, 0) + 1, key_of(q, rounds)]
+        rows = [(shared % W, shared // W), ((200000 + i) % W, (200000 + i) // W), (-1, i % H), (occupied % W, occupied // W),
+                ((210000 + i) % W, (210000 + i) // W), (shared % W, shared // W)]
+        rows = [(x1, y1, k % W, k // W) for (x1, y1), k in zip(rows, k2)][:4 + i % 3]
+        lists.append(np.array(rows, np.int32).reshape(-1, 4))
+    lmap = dict(points=pts, kf_start=np.array(kf_start, np.int32), kf_key=np.array(kf_key, np.int32),
+                kf_point=np.array(kf_point, np.int32), cur_key=cur_key, cur_point=cur_point)
+    return lmap, prm, lists, np.array([len(l) for l in lists], np.int32)
+
+
+LONG = dict(n_points=3000, n_kf=4, per_kf=1000, n_cur=700, list_len=1100)
+EDGE_SIZES = (255, 256, 257, 0, 512, 513, 1)
+EDGE_N_OUT = (511, 512, 513, 256, 768, 1025, 257)      # over lists of at least 1100; key frame 3 has no entry
+MANY_SIZES = tuple((7 * i) % 25 for i in range(300))   # 12 on average, none in every 25th key frame
+LADDERS = ((63, 0), (64, 0), (65, 0), (255, 0), (256, 0), (257, 0), (257, 1), (320, 0), (320, 3))
+LADDER_ROUNDS = 3
+
+
+def _with_n_out(case, n_out):
+    lmap, prm, lists, have = case
+    assert all(h >= n for h, n in zip(have, n_out))
+    return lmap, prm, lists, np.array(n_out, np.int32)
+
+
+# name -> (builder, cap).  n_out stays above the cap where the cap clips.
+CHUNK_CASES = {
+    "long": (lambda: scene(21, **LONG), 1100),
+    "long-cap512": (lambda: scene(21, **LONG), 512),
+    "long-cap513": (lambda: scene(21, **LONG), 513),
+    "few-points": (lambda: scene(22, n_points=300, n_kf=3, per_kf=600, n_cur=100, list_len=300), 320),
+    "many-kf": (lambda: scene(23, n_points=2000, n_kf=300, kf_sizes=MANY_SIZES, n_cur=300, list_len=40), 64),
+}
+for _n_cur in (255, 256, 257):
+    CHUNK_CASES["edges-cur%d" % _n_cur] = (
+        lambda n_cur=_n_cur: _with_n_out(scene(24, n_points=1500, n_kf=7, kf_sizes=EDGE_SIZES, n_cur=n_cur, list_len=1130),
+                                         EDGE_N_OUT), 1100)
+for _n_kf, _runs in LADDERS:
+    CHUNK_CASES["ladder-%d" % _n_kf + ("-empty" if _runs else "")] = (
+        lambda n_kf=_n_kf, runs=_runs: ladder(n_kf, LADDER_ROUNDS, runs), 8)
+SCENE_CASES = [k for k in CHUNK_CASES if not k.startswith("ladder")]
+LADDER_CASES = [k for k in CHUNK_CASES if k.startswith("ladder")]
+
+_built, _refs = {}, {}
+
+
+def chunk_case(name):
+    """-> (lmap, prm, lists, n_out, cap) of CHUNK_CASES[name], built once per process: the map's arrays and the lists
+    are shared and read-only, n_out is the caller's own"""
+    if name not in _built:
+        lmap, prm, lists, n_out = CHUNK_CASES[name][0]()
+        for a in list(lmap.values()) + lists + [n_out]:
+            a.setflags(write=False)
+        _built[name] = (lmap, prm, lists, n_out)
+    lmap, prm, lists, n_out = _built[name]
+    return lmap, prm, lists, n_out.copy(), CHUNK_CASES[name][1]
+
+
+def corr_room(lmap, lists, cap):
+    return len(lmap["cur_key"]) + len(lists) * cap
+
+
+def chunk_reference(name, forced=False):
+    """order_independent() of a case, computed once per process; forced: every key frame matched, else the gate of
+    step 3.  corr_cap = n_cur + n_kf * cap"""
+    if (name, forced) not in _refs:
+        lmap, prm, lists, n_out, cap = chunk_case(name)
+        matched = np.ones(len(lists), np.uint8) if forced else None
+        _refs[(name, forced)] = order_independent(lmap, prm, lists, n_out, cap, corr_room(lmap, lists, cap), matched=matched)
+    return _refs[(name, forced)]
+
+
+def owner_entries(lmap):
+    """-> (points that have an entry, the smallest entry index of each, its offset inside its key frame's run)"""
+    points, first = np.unique(lmap["kf_point"], return_index=True)
+    kf = np.searchsorted(lmap["kf_start"], first, side="right") - 1
+    return points, first, first - lmap["kf_start"][kf]
+
+
+def with_fault(lmap, key, at, value):
+    """a copy of the map with one value replaced; key "flags" is points["flags"]"""
+    bad = {k: v.copy() for k, v in lmap.items()}
+    if key == "flags":
+        bad["points"]["flags"][at] = value
+    else:
+        bad[key][at] = value
+    return bad
+
+
+def late_faults(lmap):
+    """What a malformed map of the long-runs scene has wrong where only a later chunk or workgroup of k_track_check
+    looks: -> [(key, at, value)], one fault per map.  a = the start of the second key frame's run."""
+    a, n_points = int(lmap["kf_start"][1]), len(lmap["points"])
+    faults = [("kf_key", a + 256, int(lmap["kf_key"][a + 255])),    # the comparison across the chunk edge
+              ("kf_point", a + 700, n_points), ("flags", 2900, 4), ("cur_key", 256, int(lmap["cur_key"][255])),
+              ("cur_point", 600, n_points)]
+    assert lmap["kf_start"][2] > a + 700 and n_points > 2900 and len(lmap["cur_key"]) > 600
+    return faults
